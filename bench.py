@@ -7,12 +7,19 @@ target Q forward on the next obs, TD error + transition store, and every 10th st
 the chunk insert into the prioritized replay. Env = ma_gym Checkers-v0 restated (oracle/env.py; ma-gym
 itself is absent), 8 agents as 4 stacked 3x8 boards; random-init weights.
 
-The JSON line also carries the QMIX learner (updates/s, configs[1]) and the MAPPO episode
-(configs[2]: rollout + GAE + 15 PPO epochs; agent-env-steps/s including training).
+A plain run (python bench.py [--gpus N --steps K --warmup W]) does only what that headline needs: it
+builds the engine, fills the replay, warms up, times ONE region of exactly K steps and prints ONE JSON
+line (rank 0). ``--dump-outputs DIR`` also writes what the last timed step left its caller as
+DIR/<name>.npy (rollout_outputs below); the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver uses
-torch.distributed.run (one process per GPU, RCCL). Envs shard across ranks with no
-data-path collective (weak scaling); rank 0 prints ONE JSON line.
+``--full`` adds every other line to the JSON: 10 timed regions instead of one (median / min / max), the
+QMIX learner (updates/s, configs[1]), the integrated train loop, the cfg1 VDN trainer, the MAPPO episode
+(configs[2]: rollout + GAE + 15 PPO epochs; agent-env-steps/s including training), the offpolicy QMix
+update, the cfg5 shapes, the roofline of the rollout kernel and the CPU baselines.
+
+For N > 1 the driver uses torch.distributed.run (one process per GPU, RCCL). Envs shard across ranks
+with no data-path collective (weak scaling).
 """
 import argparse
 import glob
@@ -229,6 +236,47 @@ def probe_ranks(world, rank):
     dist.destroy_process_group()
 
 
+def rollout_outputs(eng, store_rows=256, seed=0):
+    """{name: tensor} of what the engine's caller holds after the last rollout step t - 1: the step's actions,
+    Q(a), target max Q', rewards and dones, the next step's actions / Q(a) its behavior forward already chose,
+    the obs s_t the next step reads, both nets' hidden states, the running chunk TD, each env's store row, the
+    PER (sum tree, slot -> row table) and a fixed seeded sample of chunk-store rows (the store itself is > 1 GB)."""
+    t = eng.t
+    if eng.chunked:
+        maxq = eng.maxq_r[(t - 1) % eng.RL]
+        qsel = eng.qsel_r[(t - 1) % eng.RL]
+    else:
+        maxq = eng.maxq_buf[(t - 1) % 2] if eng.fused else eng.maxq
+        qsel = eng.qsel_buf[(t - 1) % len(eng.qsel_buf)]
+    next_act, next_q = eng._carry_views()[:2]
+    rows = torch.as_tensor(np.sort(np.random.default_rng(seed).choice(eng.store.rows, min(store_rows, eng.store.rows),
+                                                                      replace=False)), device=eng.device)
+    return {"act": eng.act, "q_taken": qsel, "target_max_q": maxq, "reward": eng.last_rew, "done": eng.last_done,
+            "next_act": next_act, "next_q_taken": next_q, "next_obs": eng.current_obs(),
+            "hidden_behavior": eng.h, "hidden_target": eng.ht, "chunk_td": eng.chunk_td, "cur_row": eng.cur_row,
+            "per_tree": eng.per.tree(), "per_slot_rows": eng.per.slot_rows(),
+            "store_sample_rows": rows, "store_sample_obs": eng.store.obs[rows], "store_sample_act": eng.store.act[rows],
+            "store_sample_rew": eng.store.rew[rows], "store_sample_done": eng.store.done[rows]}
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, tensors):
+    """Write {name: tensor} as out_dir/<name>.npy, nothing rounded: float64 and int64 tensors (store rows, far below
+    2^53) as float64, float32 and the narrow integer tensors (actions, done flags) as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -238,6 +286,12 @@ def main():
     ap.add_argument("--agents", type=int, default=8)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--epsilon", type=float, default=0.1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (rollout_outputs) as "
+                         "DIR/<name>.npy, float32 / float64 (rank 0's envs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other line (learner, train loop, cfg1, MAPPO, offpolicy QMix, cfg5, roofline, "
+                         "CPU baselines) and 10 timed regions instead of one; the options below apply with --full only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--learner-steps", type=int, default=100)
     ap.add_argument("--batch", type=int, default=32)
@@ -252,8 +306,9 @@ def main():
                     help="timed offpolicy episode-QMix updates on one GPU (0 = skip; single-GPU runs only)")
     ap.add_argument("--train-episodes", type=int, default=3,
                     help="timed episodes of the integrated QMIX train loop (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=10,
-                    help="timed regions of exactly --steps steps each; ms_per_step is their median (min / max beside)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each; ms_per_step is their median (min / max beside). "
+                         "Default 1, with --full 10")
     ap.add_argument("--cfg1-episodes", type=int, default=20,
                     help="timed training episodes of the cfg1 VDN trainer lines (0 = skip; single-GPU runs only)")
     ap.add_argument("--probe-ranks", action="store_true", help="launcher check: gloo rendezvous only, no GPU")
@@ -296,14 +351,17 @@ def main():
     eng = RolloutEngine(E, N, f1=F1, g=G, h=Hh, chunk=10, capacity=cap, seed=1234 + rank, device=dev,
                         persistent=False if shared else None)
     D = eng.D
-    from minimarl.learner import Mixer, QLearner
-    mix = Mixer(N, N * D, 64, 32, dev, seed=7)
-    tmix = Mixer(N, N * D, 64, 32, dev, seed=7)
-    learner = QLearner(eng.behavior, eng.target, mix, tmix, batch=args.batch, chunk=10, mode="qmix", device=dev)
+    learner = None
+    if args.full:   # (the learner moves the behavior net's parameters, unchanged, into its flat buffer)
+        from minimarl.learner import Mixer, QLearner
+        mix = Mixer(N, N * D, 64, 32, dev, seed=7)
+        tmix = Mixer(N, N * D, 64, 32, dev, seed=7)
+        learner = QLearner(eng.behavior, eng.target, mix, tmix, batch=args.batch, chunk=10, mode="qmix", device=dev)
     if dist:   # identical replicas: rank 0's parameters everywhere
-        dist.broadcast(learner.P, 0)
+        dist.broadcast(learner.P if learner else eng.behavior.flat, 0)
         eng.sync_target()
-        tmix.flat.copy_(mix.flat)
+        if learner:
+            tmix.flat.copy_(mix.flat)
         eng.behavior.mark_dirty()
     # setup (untimed, not counted as warm-up): fill the PER to capacity so every timed chunk insert
     # is a steady-state evicting insert
@@ -319,10 +377,11 @@ def main():
     # phase a region starts at): consecutive graph launches leave the GPU idle ~9 us each (region
     # fixed cost), which a run of chunk + single-step graph replays per region would pay ~10 times
     n_phase = eng.graph_steps()
-    for i in range(min(n_phase, max(1, args.repeats))):
+    repeats = max(1, args.repeats if args.repeats is not None else (10 if args.full else 1))
+    for i in range(min(n_phase, repeats)):
         eng.capture_region(args.steps, start=eng.t + i * args.steps)
     reps = []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(repeats):
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
@@ -348,6 +407,46 @@ def main():
     if errors:
         raise SystemExit(f"bench.py: rollout device error bits {errors:#x} after the timed regions")
     value = steps * E * N * world / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rollout_outputs(eng))
+    line = {
+        "metric": "agent-env-steps/sec (4096 envs x 8 agents per GPU, QMIX GRU-64 rollout step)",
+        "value": round(value, 1), "unit": "agent-env-steps/s", "n_gpus": world, "steps": steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
+        "repeats": len(reps), "ms_per_step_min": round(min(reps) / steps * 1e3, 4),
+        "ms_per_step_max": round(max(reps) / steps * 1e3, 4),
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (agent forward: fp16x3-split MFMA emulating f32 products, f32 accumulate)",
+        "data": "synthetic (restated ma_gym Checkers, 4 bands for 8 agents; random init)",
+        "config": {"workload": "QMIX 8-agent gridworld rollout, 4096 envs/GPU, GRU-64 agents, chunk 10, PER",
+                   "envs_per_gpu": E, "agents": N, "obs_dim": D, "f1": F1, "gru": Hh, "chunk": 10,
+                   "per_capacity_chunks": cap, "per_prefilled_chunks": fill_chunks * E,
+                   "step_launches": ("chunk-persistent launches of up to (S - 1) C = "
+                                     f"{(eng.S - 1) * eng.C} steps across chunk boundaries (env step + dual forward "
+                                     "of each step; S = 4 staging row sets), then per chunk the TD fold" if eng.chunked else
+                                     "ONE fused launch (env step + dual forward) per step" if eng.fused else
+                                     "env + dual forward per step") + " + PER insert every chunk; one captured "
+                                                                        "graph per timed region",
+                   "parallelism": f"env-shard x{world}"},
+        "rccl_world_size": world,
+        "errors": errors,
+        "full": bool(args.full),
+    }
+    if args.full:
+        line.update(full_lines(args, dist, world, rank, shared, dev, eng, learner, errors))
+    if rank == 0:
+        print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+
+
+def full_lines(args, dist, world, rank, shared, dev, eng, learner, errors):
+    """``--full``: every line besides the headline, after its timed regions, on the headline's engine (its filled
+    replay feeds the learner lines); returns the lines as {key: value} for the JSON line."""
+    from minimarl.learner import Mixer, QLearner
+    E, N, Hh, D = eng.E, eng.N, eng.H, eng.D
+    F1, G = 64, Hh
+    cap = eng.capacity
 
     # learner: one QMIX update = PER sample (B chunks) -> C-step fwd/BPTT -> [RCCL all-reduce of the
     # flat grads] -> clip/Adam -> reprioritize; replayed as two HIP graphs
@@ -782,48 +881,26 @@ def main():
     errors |= int(eng.err.item()) | (eng.per.error_word(clear=False) << 8)   # (the learner's PER updates too)
     if errors:
         raise SystemExit(f"bench.py: device error bits {errors:#x} after the learner / other lines")
-    if rank == 0:
-        line = {
-            "metric": "agent-env-steps/sec (4096 envs x 8 agents per GPU, QMIX GRU-64 rollout step)",
-            "value": round(value, 1), "unit": "agent-env-steps/s", "n_gpus": world, "steps": steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
-            "repeats": len(reps), "ms_per_step_min": round(min(reps) / steps * 1e3, 4),
-            "ms_per_step_max": round(max(reps) / steps * 1e3, 4),
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (agent forward: fp16x3-split MFMA emulating f32 products, f32 accumulate)",
-            "data": "synthetic (restated ma_gym Checkers, 4 bands for 8 agents; random init)",
-            "config": {"workload": "QMIX 8-agent gridworld rollout, 4096 envs/GPU, GRU-64 agents, chunk 10, PER",
-                       "envs_per_gpu": E, "agents": N, "obs_dim": D, "f1": F1, "gru": Hh, "chunk": 10,
-                       "per_capacity_chunks": cap, "per_prefilled_chunks": fill_chunks * E,
-                       "step_launches": ("chunk-persistent launches of up to (S - 1) C = "
-                                         f"{(eng.S - 1) * eng.C} steps across chunk boundaries (env step + dual forward "
-                                         "of each step; S = 4 staging row sets), then per chunk the TD fold" if eng.chunked else
-                                         "ONE fused launch (env step + dual forward) per step" if eng.fused else
-                                         "env + dual forward per step") + " + PER insert every chunk; one captured "
-                                                                            "graph per timed region",
-                       "parallelism": f"env-shard x{world}"},
-            "rccl_world_size": world,
-            "errors": errors,
-            "replica_checksums": replicas,
-            "learner_updates_per_s": round(upd_per_s, 1),
-            "learner": {"algo": "QMIX Train_dqn update", "batch_chunks": args.batch, "chunk": 10,
-                        "mixer_hidden": 64, "ms_per_update": round(el_l / args.learner_steps * 1e3, 4),
-                        "updates": args.learner_steps, "updates_per_graph_launch": per_replay, "grad_allreduce": (("gloo" if shared else "rccl") if dist else None),
-                        "reference_cpu_updates_per_s": 12.0,
-                        "reference_cpu_note": "reference Train_dqn.train at its own shapes (GRU-32), 8 threads of "
-                                              "the build container (BASELINE.md)",
-                        "cpu_baseline": cpu_l, "throughput_batch": big},
-            "train_loop": trainer,
-            "cfg1_vdn": cfg1,
-            "mappo": mappo,
-            "offpolicy_qmix": offq,
-            "cfg5_forward": cfg5,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
+    return {
+        "errors": errors,
+        "replica_checksums": replicas,
+        "learner_updates_per_s": round(upd_per_s, 1),
+        "learner": {"algo": "QMIX Train_dqn update", "batch_chunks": args.batch, "chunk": 10,
+                    "mixer_hidden": 64, "ms_per_update": round(el_l / args.learner_steps * 1e3, 4),
+                    "updates": args.learner_steps, "updates_per_graph_launch": per_replay,
+                    "grad_allreduce": (("gloo" if shared else "rccl") if dist else None),
+                    "reference_cpu_updates_per_s": 12.0,
+                    "reference_cpu_note": "reference Train_dqn.train at its own shapes (GRU-32), 8 CPU threads "
+                                          "(BASELINE.md)",
+                    "cpu_baseline": cpu_l, "throughput_batch": big},
+        "train_loop": trainer,
+        "cfg1_vdn": cfg1,
+        "mappo": mappo,
+        "offpolicy_qmix": offq,
+        "cfg5_forward": cfg5,
+        "roofline": roofline,
+        "cpu_baseline": cpu,
+    }
 
 
 if __name__ == "__main__":

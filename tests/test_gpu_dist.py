@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(420)
 def test_bench_two_ranks_replicas_stay_identical():
     env = dict(os.environ, MM_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5",
            "--repeats", "1", "--envs", "4096", "--learner-steps", "5", "--learner-big-steps", "0",
            "--train-episodes", "1", "--cfg1-episodes", "0", "--mappo-episodes", "1", "--offq-updates", "0",
            "--no-cfg5", "--no-cpu-baseline"]
@@ -49,7 +49,7 @@ def test_bench_rccl_branch_world_size_one():
     all-reduces, the all-gathered replica checksums) through RCCL."""
     env = dict(os.environ, MM_BENCH_DIST1="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10",
+           "127.0.0.1", "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "10",
            "--warmup", "2", "--repeats", "1", "--learner-steps", "3", "--learner-big-steps", "0", "--train-episodes",
            "1", "--cfg1-episodes", "0", "--mappo-episodes", "1", "--offq-updates", "0", "--no-cfg5", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 export MM_BENCH_DIST1=1
 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 1 --steps 20 --warmup 5 --learner-steps 10 --no-cpu-baseline --mappo-episodes 1 --no-cfg5 \
+  bench.py --full --gpus 1 --steps 20 --warmup 5 --learner-steps 10 --no-cpu-baseline --mappo-episodes 1 --no-cfg5 \
   --train-episodes 2 --cfg1-episodes 0 --offq-updates 0 --learner-big-steps 0 > gpurun_out/rccl_ws1.log 2>&1
 rc=$?
 grep '^{"metric"' gpurun_out/rccl_ws1.log | tail -1 > gpurun_out/rccl_ws1.json

@@ -4,10 +4,10 @@
 export TMPDIR=/tmp
 O=${O:-gpurun_out/prof6}
 mkdir -p $O
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 20 > $O/bench_default.log 2> $O/bench_default.err && \
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 20 > $O/bench_default.log 2> $O/bench_default.err && \
 grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json && \
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- \
-  python3 bench.py --steps 20 --warmup 20 --learner-steps 50 --no-cpu-baseline --mappo-episodes 1 > $O/stats.log 2>&1 && \
+  python3 bench.py --full --steps 20 --warmup 20 --learner-steps 50 --no-cpu-baseline --mappo-episodes 1 > $O/stats.log 2>&1 && \
 python3 profiles/summarize.py $O/stats > $O/kernel_stats.txt && \
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv && \
 bash tools/pmc_chunk.sh $O/pmc_chunk > $O/pmc_chunk.log 2>&1 && \
