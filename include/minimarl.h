@@ -574,9 +574,15 @@ int mm_clip_adam(float* P, float* G, float* m, float* v, int64_t n, int64_t n_cl
  * layout of mm_mappo_param_offsets (18 tensors: ln0_w ln0_b W1 b1 ln1_w ln1_b W2 b2 ln2_w ln2_b
  * Wih Whh bih bhh lnr_w lnr_b Wo bo + total; W1 rows padded to Dp = ceil4(D), Wo/bo to ceil4(O)).
  * Buffer arrays are [T(+1), EN] row-major with EN = envs*agents (row = t*EN + en); obs rows [.., D],
- * hiddens [.., H]. Supported: H = 32, A = 5, D in {47, 94}. */
+ * hiddens [.., H]. Supported: H = 32, A = 5, D in {47, 94}.
+ * Centralized critic (use_centralized_V; base_runner.py:70-85,155-161, rmappo_policy.py:29-33): with
+ * cent_agents = n >= 2 the critic's input is the env's share_obs, the concatenation of its n agents' obs rows
+ * (width Dc = n * obs_dim: ln0_w / ln0_b [Dc], W1 [H, Dc] with rows padded to ceil4(Dc)); the actor is
+ * unchanged. Supported: obs_dim 47 with cent_agents 2 or 8 (Dc 94 | 376), in mm_mappo_fwd ROLLOUT / VALUES and
+ * mm_mappo_grad; the TRAIN forward, mm_mappo_bwd, mm_mappo_wgrad and mm_mappo_evaluate_actions refuse it. */
 typedef struct mm_mappo_dims {
   int32_t obs_dim, hidden, n_actions;
+  int32_t cent_agents;   /* 0 | 1: the critic reads the row's own obs; n >= 2: critic input width n * obs_dim */
 } mm_mappo_dims;
 enum { MM_MAPPO_ROLLOUT = 0, MM_MAPPO_VALUES = 1, MM_MAPPO_TRAIN = 2 };
 enum { MM_MAPPO_MAX_JOBS = 16 };
@@ -609,6 +615,10 @@ typedef struct mm_mappo_fwd_args {
   int32_t mode;
   int32_t deterministic; /* rollout: take the mode (first argmax) instead of sampling (policy.act,
                             rmappo_policy.py:140-153 with deterministic=True) */
+  const float* cent_obs; /* centralized critic (dims.cent_agents = n >= 2) only. NULL: critic row r reads the n
+                            adjacent obs rows of its env, obs + (r / n) * n * D (rows of an env are adjacent: the
+                            buffer / runner layout; rows must be a multiple of n). Else critic row r reads
+                            cent_obs + r * Dc (the reference's explicit cent_obs argument) */
 } mm_mappo_fwd_args;
 typedef struct mm_mappo_bwd_args {
   const float* P[2];
@@ -628,6 +638,8 @@ typedef struct mm_mappo_bwd_args {
   int64_t en;
   int32_t T, L;
   int64_t rs;
+  const float* cent_obs; /* centralized critic only: NULL = env-adjacent rows of obs (en a multiple of n), else
+                            [T+1, EN, Dc] (see mm_mappo_fwd_args) */
 } mm_mappo_bwd_args;
 int64_t mm_mappo_param_count(const mm_mappo_dims* d, int32_t net);
 int mm_mappo_param_offsets(const mm_mappo_dims* d, int32_t net, int64_t offs[19]);

@@ -646,7 +646,7 @@ struct MappoShape {
   using GC = MGeo<D, H, 1>;
   static int fwd(const mm_mappo_fwd_args* a, hipStream_t s) {
     if (a->mode != MM_MAPPO_TRAIN && H == 32) {   // rollout / get_values: the MFMA forward (mappo_grad.hip)
-      const mm_mappo_dims d{D, H, A};
+      const mm_mappo_dims d{D, H, A, 0};
       return mappo_roll_fwd(&d, a, s);
     }
     const int64_t n = a->mode == MM_MAPPO_TRAIN ? (int64_t)(a->T / a->L) * a->en : a->rows;
@@ -746,8 +746,16 @@ static int mappo_eval_launch(const mm_mappo_fwd_args* a, const int32_t* act, con
   return MM_OK;
 }
 
+// the per-thread TRAIN forward / BPTT / weight-gradient path: decentralized critic only
 #define MM_MAPPO_DISPATCH(d, CALL)                                                  \
   do {                                                                              \
+    if (mm::mappo_cent_agents(d) > 1) {                                             \
+      mm::set_error("mappo: the centralized critic (cent_agents=%d, critic input width %d) is not supported by the " \
+                    "non-fused training path (TRAIN forward, mm_mappo_bwd, mm_mappo_wgrad, "                        \
+                    "mm_mappo_evaluate_actions); use mm_mappo_grad",                                                \
+                    (d)->cent_agents, (d)->cent_agents * (d)->obs_dim);                                             \
+      return MM_EINVAL;                                                             \
+    }                                                                               \
     if ((d)->hidden == 32 && (d)->n_actions == 5 && (d)->obs_dim == 47) {           \
       using SH = mm::MappoShape<47, 32, 5>;                                           \
       return CALL;                                                                  \
@@ -756,18 +764,20 @@ static int mappo_eval_launch(const mm_mappo_fwd_args* a, const int32_t* act, con
       using SH = mm::MappoShape<94, 32, 5>;                                           \
       return CALL;                                                                  \
     }                                                                               \
-    mm::set_error("mappo: unsupported dims D=%d H=%d A=%d (supported: D 47|94, H 32, A 5)", (d)->obs_dim, \
-              (d)->hidden, (d)->n_actions);                                         \
-    return MM_EINVAL;                                                               \
+    return mm::mappo_dims_error(d);                                                 \
   } while (0)
 
+// input width of a net: the critic of a centralized policy reads cent_agents obs rows
+static int net_in_dim(const mm_mappo_dims* d, int net) { return net == 1 ? d->obs_dim * mappo_cent_agents(d) : d->obs_dim; }
+
 static int64_t param_count(const mm_mappo_dims* d, int net) {
-  if (d->hidden == 32 && d->n_actions == 5 && d->obs_dim == 47)
-    return net == 0 ? MGeo<47, 32, 5>::total : MGeo<47, 32, 1>::total;
-  if (d->hidden == 32 && d->n_actions == 5 && d->obs_dim == 94)
-    return net == 0 ? MGeo<94, 32, 5>::total : MGeo<94, 32, 1>::total;
-  return -1;
+  if (!mappo_dims_supported(d)) return -1;
+  const int Dp = (net_in_dim(d, net) + 3) & ~3, H = d->hidden, Op = ((net == 0 ? d->n_actions : 1) + 3) & ~3;
+  return 2 * Dp + (int64_t)H * Dp + 14 * H + 7 * H * H + (int64_t)Op * H + Op;   // MGeo::total
 }
+static_assert(MGeo<47, 32, 5>::total == 2 * 48 + 32 * 48 + 14 * 32 + 7 * 32 * 32 + 8 * 32 + 8 &&
+                  MGeo<376, 32, 1>::total == 2 * 376 + 32 * 376 + 14 * 32 + 7 * 32 * 32 + 4 * 32 + 4,
+              "param_count restates MGeo::total");
 
 }  // namespace mm
 
@@ -781,10 +791,9 @@ int64_t mm_mappo_param_count(const mm_mappo_dims* d, int32_t net) {
 
 int mm_mappo_param_offsets(const mm_mappo_dims* d, int32_t net, int64_t offs[19]) {
   MM_REQUIRE(d && offs && (net == 0 || net == 1), "mappo_param_offsets: bad args");
-  MM_REQUIRE(mm::param_count(d, net) > 0, "mappo: unsupported dims D=%d H=%d A=%d", d->obs_dim, d->hidden,
-             d->n_actions);
+  if (mm::param_count(d, net) <= 0) return mm::mappo_dims_error(d);
   const int H = d->hidden, O = net == 0 ? d->n_actions : 1;
-  const int Dp = (d->obs_dim + 3) & ~3, Op = (O + 3) & ~3;
+  const int Dp = (mm::net_in_dim(d, net) + 3) & ~3, Op = (O + 3) & ~3;
   int64_t c = 0;
   const int64_t sz[18] = {Dp, Dp, (int64_t)H * Dp, H, H, H, (int64_t)H * H, H, H, H, 3ll * H * H, 3ll * H * H,
                           3 * H, 3 * H, H, H, (int64_t)Op * H, Op};
@@ -813,6 +822,11 @@ int mm_mappo_fwd(const mm_mappo_dims* d, const mm_mappo_fwd_args* a, mm_stream_t
   MM_REQUIRE(a->mode != MM_MAPPO_TRAIN ||
                  (a->L > 0 && a->T % a->L == 0 && a->mask && a->net[0].save && a->net[1].save && a->rs >= a->T * a->en),
              "mappo_fwd: train mode needs L | T, masks, save buffers and rs >= T*EN");
+  if (!mm::mappo_dims_supported(d)) return mm::mappo_dims_error(d);
+  const int rc = mm::mappo_cent_check(d, a->obs, a->cent_obs, a->mode == MM_MAPPO_TRAIN ? a->en : a->rows, "mappo_fwd");
+  if (rc != MM_OK) return rc;
+  // centralized critic: the MFMA forward (the TRAIN forward refuses it below)
+  if (mm::mappo_cent_agents(d) > 1 && a->mode != MM_MAPPO_TRAIN) return mm::mappo_roll_fwd(d, a, (hipStream_t)s);
   MM_MAPPO_DISPATCH(d, SH::fwd(a, (hipStream_t)s));
 }
 
@@ -838,7 +852,7 @@ int mm_mappo_evaluate_actions(const mm_mappo_dims* d, const mm_mappo_fwd_args* a
 }
 
 int64_t mm_mappo_wgrad_partial_count(const mm_mappo_dims* d, int64_t rs) {
-  if (!d || mm::param_count(d, 0) < 0) return -1;
+  if (!d || mm::param_count(d, 0) < 0 || mm::mappo_cent_agents(d) > 1) return -1;
   if (d->obs_dim == 47) return mm::MappoShape<47, 32, 5>::partial_count(rs);
   return mm::MappoShape<94, 32, 5>::partial_count(rs);
 }

@@ -270,6 +270,60 @@ __device__ __forceinline__ void ln0_stats(const float (&x)[DT][16], float& mu, f
   rs = 1.0f / sqrtf(xsum(d2) / (float)D + kLnEps);
 }
 
+// ---- centralized critic (use_centralized_V): input = the env's share_obs, its NA agents' obs rows concatenated
+// (base_runner.py:155-161), width D = NA * obs_dim. Rows of an env are adjacent in the buffer (row = e * NA + a), so
+// the share_obs of row r is the D contiguous floats at obs + (r / NA) * D: no share_obs array exists. An explicit
+// cent_obs [rows, D] (the reference's get_actions / get_values signature) is read instead when given.
+template <int D, int NA>
+__device__ __forceinline__ const float* in_row(const float* __restrict__ obs, const float* __restrict__ cent,
+                                               int64_t row) {
+  if constexpr (NA <= 1)
+    return obs + row * D;
+  else
+    return cent ? cent + row * D : obs + (row / NA) * D;
+}
+// One 32-feature tile of a wide input row (feature 32 t + kperm(q, h); zero beyond D). The wide rows do not stay in
+// registers (D 376: 192 VGPRs): the LN0 statistics and the L1 products each stream the row's tiles again (L1 / L2
+// hits after the first pass). D is even and the rows start 8-byte aligned: 8-byte loads.
+template <int D>
+__device__ __forceinline__ void load_obs_tile(const float* __restrict__ orow, int t, float (&x)[16]) {
+  static_assert(D % 2 == 0, "wide input rows are read in pairs");
+  const int h = lane_h();
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int f = 32 * t + kperm(2 * p, h);   // even; a pair lies wholly below or beyond D
+    const float2 v = *reinterpret_cast<const float2*>(orow + (f < D ? f : 0));
+    x[2 * p] = f < D ? v.x : 0.f;
+    x[2 * p + 1] = f < D ? v.y : 0.f;
+  }
+}
+// ln0_stats' arithmetic (the same summation order) over streamed tiles
+template <int D, int DT>
+__device__ __forceinline__ void ln0_stats_stream(const float* __restrict__ orow, float& mu, float& rs) {
+  const int h = lane_h();
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < DT; ++t) {
+    float x[16];
+    load_obs_tile<D>(orow, t, x);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += x[q];
+  }
+  mu = xsum(s) / (float)D;
+  float d2 = 0.f;
+#pragma unroll
+  for (int t = 0; t < DT; ++t) {
+    float x[16];
+    load_obs_tile<D>(orow, t, x);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const float d = 32 * t + kperm(q, h) < D ? x[q] - mu : 0.f;
+      d2 = fmaf(d, d, d2);
+    }
+  }
+  rs = 1.0f / sqrtf(xsum(d2) / (float)D + kLnEps);
+}
+
 // Offsets of the MLP's LayerNorm / bias vectors relative to ln0w (the same in both LDS images)
 template <int D>
 struct LnOff {
@@ -280,7 +334,7 @@ struct LnOff {
 
 // LN0 -> L1 -> ReLU -> LN1 -> L2 -> ReLU (-> LN2 statistics) of one row tile in act-frag. W1 / W2: the padded
 // LDS rows (pitches P1 / PW); lv: the LayerNorm / bias vectors (LnOff).
-template <int D, int O>
+template <int D, int O, bool WIDE = false>
 struct Mlp {
   using G = Geo<D, O>;
   using LO = LnOff<D>;
@@ -289,18 +343,25 @@ struct Mlp {
 
   __device__ __forceinline__ void run(const float* W1, const float* W2, const float* lv, const float* __restrict__ orow) {
     const int h = lane_h();
-    float x[DT][16];
-    load_obs<D, DT>(orow, x);
-    ln0_stats<D, DT>(x, mu0, rs0);
+    // WIDE: the row is not kept (one tile buffer, the tiles streamed again by load_obs_tile)
+    float x[WIDE ? 1 : DT][16];
+    if constexpr (WIDE) {
+      ln0_stats_stream<D, DT>(orow, mu0, rs0);
+    } else {
+      load_obs<D, DT>(orow, x);
+      ln0_stats<D, DT>(x, mu0, rs0);
+    }
     f32x16 acc;
     zero16(acc);
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
+      if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);
+      const float (&xt)[16] = x[WIDE ? 0 : t];
       float f0[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int f = 32 * t + kperm(q, h);
-        f0[q] = (x[t][q] - mu0) * rs0 * lv[LO::ln0w + f] + lv[LO::ln0b + f];
+        f0[q] = (xt[q] - mu0) * rs0 * lv[LO::ln0w + f] + lv[LO::ln0b + f];
       }
       mm_rows<G::P1>(W1 + 32 * t, f0, acc, kgroups(D - 32 * t));
     }
@@ -523,9 +584,13 @@ struct GeoM {
   static constexpr int DT = G::DT;
   static constexpr int W1 = 0, W2 = W1 + DT * HBLK, W2T = W2 + HBLK, W1T = W2T + HBLK, vec = W1T + DT * HBLK,
                        nblk = vec / HBLK, ln0w = vec, wsc = vec + (G::bih - G::ln0w), scr = wsc + 8;
-  // waves per block: 8 (2 per SIMD) where the registers allow it (DT <= 2) and the tiles fit the 160 KB of LDS
-  static constexpr int MW = (DT <= 2 && (scr + 8 * MT * TILE) * 4 <= 160 * 1024) ? 8 : 4;
-  static constexpr int total = scr + MW * MT * TILE;
+  // waves per block: 8 (2 per SIMD) where the registers allow it (DT <= 2) and the tiles fit the 160 KB of LDS;
+  // 3 where the image of a wide first layer (D 376: W1 and W1^T are 48 KB each) leaves room for no more
+  static constexpr int MW = (DT <= 2 && (scr + 8 * MT * TILE) * 4 <= 160 * 1024) ? 8
+                            : (scr + 4 * MT * TILE) * 4 <= 160 * 1024            ? 4
+                                                                                  : 3;
+  static constexpr int total_for(int mw) { return scr + mw * MT * TILE; }
+  static constexpr int total = total_for(MW);
 };
 static_assert(GeoH<47, 5>::W2 == GeoM<47, 5>::W2 && GeoH<94, 5>::W2 == GeoM<94, 5>::W2, "W1 / W2 offsets");
 
@@ -609,7 +674,7 @@ __device__ void stage_h(float* sm, const float* __restrict__ P) {
 
 // LN0 -> L1 -> ReLU -> LN1 -> L2 -> ReLU (-> LN2 statistics) of one row tile on a split image (GI: GeoH or GeoM; both
 // hold W1 / W2 / the MLP vectors / the scales at the same places): Mlp's arithmetic with fp16x3 products
-template <int D, class GI>
+template <int D, class GI, bool WIDE = false>
 struct MlpH {
   using LO = LnOff<D>;
   static constexpr int DT = GI::DT;
@@ -619,19 +684,26 @@ struct MlpH {
     const int h = lane_h();
     const float* lv = sm + GI::ln0w;
     const float sw = sm[GI::wsc];
-    float x[DT][16];
-    load_obs<D, DT>(orow, x);
-    ln0_stats<D, DT>(x, mu0, rs0);
+    // WIDE: the row is not kept (one tile buffer, the tiles streamed again by load_obs_tile)
+    float x[WIDE ? 1 : DT][16];
+    if constexpr (WIDE) {
+      ln0_stats_stream<D, DT>(orow, mu0, rs0);
+    } else {
+      load_obs<D, DT>(orow, x);
+      ln0_stats<D, DT>(x, mu0, rs0);
+    }
     f32x16 acc;
     zero16(acc);
     const float s0 = sm[GI::wsc + 1];
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
+      if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);
+      const float (&xt)[16] = x[WIDE ? 0 : t];
       float f0[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int f = 32 * t + kperm(q, h);
-        f0[q] = (x[t][q] - mu0) * rs0 * lv[LO::ln0w + f] + lv[LO::ln0b + f];
+        f0[q] = (xt[q] - mu0) * rs0 * lv[LO::ln0w + f] + lv[LO::ln0b + f];
       }
       S16 sf;
       split16s(f0, s0, sf);
@@ -658,12 +730,12 @@ struct MlpH {
   }
 };
 // x2 = LN2(a2) of one row tile on pass G's image (pass G's step 1)
-template <int D, int O>
+template <int D, int O, bool WIDE>
 __device__ __forceinline__ void mlp_x2_h(const float* sm, const float* __restrict__ orow, float (&x2)[16]) {
   using LO = LnOff<D>;
   const int h = lane_h();
   const float* lv = sm + GeoH<D, O>::ln0w;
-  MlpH<D, GeoH<D, O>> mp;
+  MlpH<D, GeoH<D, O>, WIDE> mp;
   mp.run(sm, orow);
 #pragma unroll
   for (int q = 0; q < 16; ++q)
@@ -705,7 +777,7 @@ struct GruH {
 };
 
 // ---------------------------------------------------------------- pass G: recurrent part
-template <int D, int A, int O>
+template <int D, int A, int O, int NA = 1>
 __device__ void gru_body(const GradArgs& k, int net, float* sm) {
   using GH = GeoH<D, O>;
   using F = MGeo<D, H, O>;
@@ -759,7 +831,7 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm) {
       st16(hs + l * 1024, hc);
       const float* smo = sm + opaque0();
       float x2[16];
-      mlp_x2_h<D, O>(smo, a.obs + row * D, x2);
+      mlp_x2_h<D, O, (NA > 1)>(smo, in_row<D, NA>(a.obs, a.cent_obs, row), x2);
       st16(xs + l * 1024, x2);         // the GRU input of every step, for step 2 (no MLP recompute there)
       if (l + 1 < L) {
         GruH<D, O> gr;
@@ -1100,9 +1172,10 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm) {
 // dW2 / db2 / LN2 parameters from d x2 (pass G's output), dx1 = W2^T da2 -> LN1 backward, dW1 / db1, df0 = W1^T da1 ->
 // LN0 parameters. Weight-gradient operands are transposed through 3 LDS tiles per wave (chunks on k); the vector
 // operands of the W^T products take one scale per column (row), those of the weight gradients one per wave tile.
-template <int D, int O>
+template <int D, int O, int MWV, int NA = 1>
 __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
   using GM = GeoM<D, O>;
+  constexpr bool WIDE = NA > 1;
   using F = MGeo<D, H, O>;
   using LO = LnOff<D>;
   constexpr int DT = GM::DT;
@@ -1114,7 +1187,6 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
   float* S1 = S0 + TILE;
   float* S2 = S1 + TILE;
   const int64_t R = (int64_t)a.T * a.en, ntile = (R + 31) / 32;
-  constexpr int MWV = GM::MW;
   const int wg = blockIdx.x * MWV + w, nwg = gridDim.x * MWV;
   const float* dx2i = k.dx2 + (int64_t)net * R * 32;
 
@@ -1139,8 +1211,9 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) dxv[q] = 0.f;
     }
-    MlpH<D, GM> mp;
-    mp.run(smb, a.obs + row * D);
+    const float* __restrict__ orow = in_row<D, NA>(a.obs, a.cent_obs, row);
+    MlpH<D, GM, WIDE> mp;
+    mp.run(smb, orow);
     // ---- LN2 backward (x2 = LN2(a2), a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
     float da[16], xh[16], tt[16], f1[16];
 #pragma unroll
@@ -1218,15 +1291,17 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
       S16 sd;
       split16s(da1, c_b, sd);
       const float u_b = 1.0f / (sw * c_b), u_w = 1.0f / (s_a1 * s_f0);
-      float x[DT][16];
-      load_obs<D, DT>(a.obs + row * D, x);
+      float x[WIDE ? 1 : DT][16];
+      if constexpr (!WIDE) load_obs<D, DT>(orow, x);
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
         float x0[16], f0[16], dfv[16];
+        if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);   // (streamed again: the wide row is not kept)
+        const float (&xt)[16] = x[WIDE ? 0 : t];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int f = 32 * t + kperm(q, h);
-          x0[q] = (x[t][q] - mp.mu0) * mp.rs0;
+          x0[q] = (xt[q] - mp.mu0) * mp.rs0;
           f0[q] = x0[q] * lv[LO::ln0w + f] + lv[LO::ln0b + f];
         }
         tput(S0, f0);
@@ -1322,7 +1397,7 @@ __device__ void stage_fwd(float* sm, const float* __restrict__ P) {
   __syncthreads();
 }
 
-template <int D, int A, int O>
+template <int D, int A, int O, int NA = 1>
 __device__ void roll_body(const mm_mappo_fwd_args& a, int net, float* sm) {
   using G = Geo<D, O>;
   stage_fwd<D, O>(sm, a.net[net].P);
@@ -1338,8 +1413,8 @@ __device__ void roll_body(const mm_mappo_fwd_args& a, int net, float* sm) {
     const float* smo = sm + opaque0();
     float x2[16], hc[16];
     {
-      Mlp<D, O> mp;
-      mp.run(smo + G::W1, smo + G::W2, smo + G::ln0w, a.obs + row * D);
+      Mlp<D, O, (NA > 1)> mp;
+      mp.run(smo + G::W1, smo + G::W2, smo + G::ln0w, in_row<D, NA>(a.obs, a.cent_obs, row));
       mp.x2(smo + G::ln0w, x2);
     }
     ld_row32(io.h_in, row, hc);
@@ -1409,23 +1484,30 @@ __device__ void roll_body(const mm_mappo_fwd_args& a, int net, float* sm) {
   }
 }
 
-template <int D, int A>
-__global__ __launch_bounds__(256, 2) void mappo_roll_kernel(mm_mappo_fwd_args a) {
+// NA >= 2: the centralized critic (input width NA * D; the actor keeps D). One launch runs both nets, so every block
+// gets the larger LDS image: 2 blocks per CU where two of them fit the 160 KB, else 1 (Dc 376: 113 KB)
+template <int D, int A, int NA>
+constexpr int roll_lds() {
+  return std::max(Geo<D, A>::scr, Geo<D * NA, 1>::scr) * 4;
+}
+template <int D, int A, int NA>
+__global__ __launch_bounds__(256, (2 * roll_lds<D, A, NA>() <= 160 * 1024 ? 2 : 1)) void mappo_roll_kernel(
+    mm_mappo_fwd_args a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int net = (int)blockIdx.y + (a.mode == MM_MAPPO_VALUES ? 1 : 0);
   if (net == 0)
     roll_body<D, A, A>(a, 0, sm);
   else
-    roll_body<D, A, 1>(a, 1, sm);
+    roll_body<D * NA, A, 1, NA>(a, 1, sm);
 }
 
-template <int D, int A>
+template <int D, int A, int NA>
 static int roll_fwd(const mm_mappo_fwd_args* a, hipStream_t s) {
-  constexpr size_t lds = (size_t)Geo<D, A>::scr * 4;
-  static_assert(Geo<D, A>::scr == Geo<D, 1>::scr, "actor / critic LDS images differ");
+  constexpr size_t lds = (size_t)roll_lds<D, A, NA>();
+  static_assert(lds <= 160 * 1024, "LDS budget");
   static const int attr_rc = [&]() -> int {
-    MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_roll_kernel<D, A>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
+    MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_roll_kernel<D, A, NA>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return MM_OK;
   }();
   if (attr_rc != MM_OK) return attr_rc;
@@ -1433,27 +1515,34 @@ static int roll_fwd(const mm_mappo_fwd_args* a, hipStream_t s) {
   const int64_t ntile = (a->rows + 31) / 32;
   const int nets = a->mode == MM_MAPPO_VALUES ? 1 : 2;
   const unsigned nb = (unsigned)std::min<int64_t>((ntile + 3) / 4, 1024);
-  hipLaunchKernelGGL((mappo_roll_kernel<D, A>), dim3(nb, nets), dim3(256), lds, s, *a);
+  hipLaunchKernelGGL((mappo_roll_kernel<D, A, NA>), dim3(nb, nets), dim3(256), lds, s, *a);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
 }
 
-template <int D, int A>
+template <int D, int A, int NA>
 __global__ __launch_bounds__(64 * GW, 1) void mappo_grad_gru_kernel(GradArgs k) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   if (blockIdx.y == 0)
     gru_body<D, A, A>(k, 0, sm);
   else
-    gru_body<D, A, 1>(k, 1, sm);
+    gru_body<D * NA, A, 1, NA>(k, 1, sm);
 }
 
-template <int D, int A>
-__global__ __launch_bounds__((64 * GeoM<D, A>::MW), 1) void mappo_grad_mlp_kernel(GradArgs k) {
+// waves per block of pass M: one launch runs both nets, so the fewer of the two images' (a wide critic's 3)
+template <int D, int A, int NA>
+constexpr int mlp_waves() {
+  return std::min(GeoM<D, A>::MW, GeoM<D * NA, 1>::MW);
+}
+
+template <int D, int A, int NA>
+__global__ __launch_bounds__((64 * mlp_waves<D, A, NA>()), 1) void mappo_grad_mlp_kernel(GradArgs k) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int MW = mlp_waves<D, A, NA>();
   if (blockIdx.y == 0)
-    mlp_body<D, A>(k, 0, sm);
+    mlp_body<D, A, MW>(k, 0, sm);
   else
-    mlp_body<D, 1>(k, 1, sm);
+    mlp_body<D * NA, 1, MW, NA>(k, 1, sm);
 }
 
 // grad[p] = sum over the partials of both passes [b][p], fixed order
@@ -1469,24 +1558,26 @@ __global__ __launch_bounds__(256) void mappo_grad_sum_kernel(const float* __rest
   (net == 0 ? g0 : g1)[p] = s;
 }
 
-template <int D, int A>
+template <int D, int A, int NA>
 struct GradShape {
-  static int64_t pstride() { return ((int64_t)MGeo<D, H, A>::total + 3) & ~3ll; }
+  static constexpr int DC = D * NA, MW = mlp_waves<D, A, NA>();
+  static constexpr int n0 = MGeo<D, H, A>::total, n1 = MGeo<DC, H, 1>::total;
+  static int64_t pstride() { return ((int64_t)std::max(n0, n1) + 3) & ~3ll; }
   static int64_t hseq_count(int L) { return 2ll * NB * GW * 2 * L * 1024; }
   static int64_t scratch(int L, int T, int64_t en) {
     return hseq_count(L) + 2ll * T * en * 32 + 2ll * 2 * NB * pstride();
   }
   static int run(const mm_mappo_bwd_args* a, const float* ha, const float* hc, float* ga, float* gc, float* scratch,
                  hipStream_t s) {
-    constexpr size_t lds_g = (size_t)GeoH<D, A>::total * 4, lds_m = (size_t)GeoM<D, A>::total * 4;
-    static_assert(GeoH<D, A>::total == GeoH<D, 1>::total && GeoM<D, A>::total == GeoM<D, 1>::total,
-                  "actor / critic LDS images differ");
-    static_assert(GeoH<D, A>::total * 4 <= 160 * 1024 && GeoM<D, A>::total * 4 <= 160 * 1024, "LDS budget");
+    // one launch per pass runs both nets: the larger of the two LDS images
+    constexpr size_t lds_g = (size_t)std::max(GeoH<D, A>::total, GeoH<DC, 1>::total) * 4;
+    constexpr size_t lds_m = (size_t)std::max(GeoM<D, A>::total_for(MW), GeoM<DC, 1>::total_for(MW)) * 4;
+    static_assert(lds_g <= 160 * 1024 && lds_m <= 160 * 1024, "LDS budget");
     // thread-safe one-time setup (a function-local static's initialiser runs once); the sizes are compile-time
     static const int attr_rc = [&]() -> int {
-      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_gru_kernel<D, A>,
+      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_gru_kernel<D, A, NA>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
-      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_mlp_kernel<D, A>,
+      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_mlp_kernel<D, A, NA>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
       return MM_OK;
     }();
@@ -1499,12 +1590,11 @@ struct GradShape {
     k.dx2 = scratch + hseq_count(a->L);
     k.partial = k.dx2 + 2ll * a->T * a->en * 32;
     k.pstride = pstride();
-    hipLaunchKernelGGL((mappo_grad_gru_kernel<D, A>), dim3(NB, 2), dim3(64 * GW), lds_g, s, k);
+    hipLaunchKernelGGL((mappo_grad_gru_kernel<D, A, NA>), dim3(NB, 2), dim3(64 * GW), lds_g, s, k);
     MM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((mappo_grad_mlp_kernel<D, A>), dim3(NB, 2), dim3(64 * GeoM<D, A>::MW), lds_m, s, k);
+    hipLaunchKernelGGL((mappo_grad_mlp_kernel<D, A, NA>), dim3(NB, 2), dim3(64 * MW), lds_m, s, k);
     MM_HIP_CHECK(hipGetLastError());
-    const int n0 = MGeo<D, H, A>::total, n1 = MGeo<D, H, 1>::total;
-    hipLaunchKernelGGL(mappo_grad_sum_kernel, dim3((n0 + 255) / 256, 2), dim3(256), 0, s, k.partial, 2 * NB,
+    hipLaunchKernelGGL(mappo_grad_sum_kernel, dim3((std::max(n0, n1) + 255) / 256, 2), dim3(256), 0, s, k.partial, 2 * NB,
                        k.pstride, n0, n1, ga, gc);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
@@ -1513,19 +1603,33 @@ struct GradShape {
 
 }  // namespace mgr
 
-// the rollout / get_values forward on MFMA (mappo.hip routes MM_MAPPO_ROLLOUT / VALUES here for H 32, D 47 | 94, A 5)
+// (obs_dim, critic agents) of the instantiated shapes; the critic agents are 1 for a decentralized critic
+#define MM_MAPPO_GRAD_SHAPES(d, CALL)                                                  \
+  do {                                                                                 \
+    const int D_ = (d)->obs_dim, n_ = (d)->cent_agents >= 2 ? (d)->cent_agents : 1;    \
+    if (D_ == 47 && n_ == 1) return CALL(47, 1);                                       \
+    if (D_ == 94 && n_ == 1) return CALL(94, 1);                                       \
+    if (D_ == 47 && n_ == 2) return CALL(47, 2);                                       \
+    if (D_ == 47 && n_ == 8) return CALL(47, 8);                                       \
+  } while (0)
+
+// the rollout / get_values forward on MFMA (mappo.hip routes MM_MAPPO_ROLLOUT / VALUES here for the supported dims)
 int mappo_roll_fwd(const mm_mappo_dims* d, const mm_mappo_fwd_args* a, hipStream_t s) {
-  if (d->obs_dim == 47) return mgr::roll_fwd<47, 5>(a, s);
-  return mgr::roll_fwd<94, 5>(a, s);
+#define MM_CALL(D, N) mgr::roll_fwd<D, 5, N>(a, s)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  set_error("mappo: unsupported dims");
+  return MM_EINVAL;
 }
 }  // namespace mm
 
 extern "C" {
 
 int64_t mm_mappo_grad_scratch_count(const mm_mappo_dims* d, int32_t L, int32_t T, int64_t en) {
-  if (!d || L <= 0 || T <= 0 || en <= 0 || d->hidden != 32 || d->n_actions != 5) return -1;
-  if (d->obs_dim == 47) return mm::mgr::GradShape<47, 5>::scratch(L, T, en);
-  if (d->obs_dim == 94) return mm::mgr::GradShape<94, 5>::scratch(L, T, en);
+  if (!d || L <= 0 || T <= 0 || en <= 0 || !mm::mappo_dims_supported(d)) return -1;
+#define MM_CALL(D, N) mm::mgr::GradShape<D, 5, N>::scratch(L, T, en)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
   return -1;
 }
 
@@ -1538,12 +1642,14 @@ int mm_mappo_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const floa
              "mappo_grad: null pointer");
   MM_REQUIRE(((uintptr_t)h_actor & 15) == 0 && ((uintptr_t)h_critic & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
              "mappo_grad: hiddens and scratch must be 16-byte aligned");
-  MM_REQUIRE(d->hidden == 32 && d->n_actions == 5 && (d->obs_dim == 47 || d->obs_dim == 94),
-             "mappo_grad: unsupported dims D=%d H=%d A=%d (supported: D 47|94, H 32, A 5)", d->obs_dim, d->hidden,
-             d->n_actions);
-  if (d->obs_dim == 47)
-    return mm::mgr::GradShape<47, 5>::run(a, h_actor, h_critic, grad_actor, grad_critic, scratch, (hipStream_t)s);
-  return mm::mgr::GradShape<94, 5>::run(a, h_actor, h_critic, grad_actor, grad_critic, scratch, (hipStream_t)s);
+  if (!mm::mappo_dims_supported(d)) return mm::mappo_dims_error(d);
+  const int rc = mm::mappo_cent_check(d, a->obs, a->cent_obs, a->en, "mappo_grad");
+  if (rc != MM_OK) return rc;
+#define MM_CALL(D, N) \
+  mm::mgr::GradShape<D, 5, N>::run(a, h_actor, h_critic, grad_actor, grad_critic, scratch, (hipStream_t)s)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  return mm::mappo_dims_error(d);
 }
 
 }  // extern "C"

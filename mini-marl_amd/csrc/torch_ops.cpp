@@ -375,8 +375,9 @@ void vdn_sum(const at::Tensor& q, const c10::optional<at::Tensor>& act, at::Tens
 
 // ------------------------------------------------------------------ MAPPO actor / critic
 mm_mappo_dims mappo_dims(const std::vector<int64_t>& d, const at::Tensor& actor_P, const at::Tensor& critic_P) {
-  TORCH_CHECK(d.size() == 3, "MAPPO dims must be [obs_dim, hidden, n_actions]");
-  mm_mappo_dims m{(int32_t)d[0], (int32_t)d[1], (int32_t)d[2]};
+  TORCH_CHECK(d.size() == 3 || d.size() == 4, "MAPPO dims must be [obs_dim, hidden, n_actions(, cent_agents)]");
+  // cent_agents n >= 2: centralized critic over the n adjacent obs rows of an env (rows grouped by env)
+  mm_mappo_dims m{(int32_t)d[0], (int32_t)d[1], (int32_t)d[2], d.size() == 4 ? (int32_t)d[3] : 0};
   need(actor_P, at::kFloat, "actor_P");
   need(critic_P, at::kFloat, "critic_P");
   same_device(actor_P, critic_P, "critic_P");

@@ -21,6 +21,43 @@ struct MGeo {
   static constexpr int total = bo + Op;
 };
 
+// Supported MAPPO shapes (host): H 32, A 5, D 47 | 94 with a decentralized critic (cent_agents 0 | 1), D 47 with a
+// centralized critic over 2 or 8 agents (critic input width 94 | 376).
+inline int mappo_cent_agents(const mm_mappo_dims* d) { return d->cent_agents >= 2 ? d->cent_agents : 1; }
+inline bool mappo_dims_supported(const mm_mappo_dims* d) {
+  if (d->hidden != 32 || d->n_actions != 5 || d->cent_agents < 0) return false;
+  const int n = mappo_cent_agents(d);
+  return n == 1 ? (d->obs_dim == 47 || d->obs_dim == 94) : (d->obs_dim == 47 && (n == 2 || n == 8));
+}
+inline int mappo_dims_error(const mm_mappo_dims* d) {
+  set_error("mappo: unsupported dims D=%d H=%d A=%d cent_agents=%d (supported: H 32, A 5, D 47|94; centralized "
+            "critic: D 47 with cent_agents 2|8, critic input width 94|376)",
+            d->obs_dim, d->hidden, d->n_actions, d->cent_agents);
+  return MM_EINVAL;
+}
+// centralized critic: the grouped form (cent_obs NULL) needs env-adjacent rows, both forms 8-byte aligned rows
+inline int mappo_cent_check(const mm_mappo_dims* d, const float* obs, const float* cent_obs, int64_t rows,
+                            const char* who) {
+  const int n = mappo_cent_agents(d);
+  if (n == 1) {
+    if (cent_obs) {
+      set_error("%s: cent_obs given but dims.cent_agents is %d (decentralized critic)", who, d->cent_agents);
+      return MM_EINVAL;
+    }
+    return MM_OK;
+  }
+  if (!cent_obs && rows % n != 0) {
+    set_error("%s: centralized critic without cent_obs reads the %d adjacent rows of an env: rows (%lld) must be a "
+              "multiple of cent_agents", who, n, (long long)rows);
+    return MM_EINVAL;
+  }
+  if (((uintptr_t)(cent_obs ? cent_obs : obs) & 7) != 0) {
+    set_error("%s: centralized critic input must be 8-byte aligned", who);
+    return MM_EINVAL;
+  }
+  return MM_OK;
+}
+
 // forward save fields (tiled SoA, see soa_col; row = t*EN + en), per net
 template <int H, int O>
 struct SF {

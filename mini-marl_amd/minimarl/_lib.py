@@ -304,7 +304,7 @@ MM_MLOSS_POLICY, MM_MLOSS_ENTROPY, MM_MLOSS_VALUE, MM_MLOSS_RATIO = range(4)
 
 
 class MappoDims(ctypes.Structure):
-    _fields_ = [("obs_dim", c_i32), ("hidden", c_i32), ("n_actions", c_i32)]
+    _fields_ = [("obs_dim", c_i32), ("hidden", c_i32), ("n_actions", c_i32), ("cent_agents", c_i32)]
 
 
 class MappoNetIO(ctypes.Structure):
@@ -315,7 +315,7 @@ class MappoFwdArgs(ctypes.Structure):
     _fields_ = [("net", MappoNetIO * 2), ("obs", c_vp), ("mask", c_vp), ("act_in", c_vp), ("act_out", c_vp),
                 ("u", c_vp), ("seed", c_u64), ("counter_ptr", c_vp), ("counter", c_u64), ("rows", c_i64),
                 ("en", c_i64), ("T", c_i32), ("L", c_i32), ("rs", c_i64), ("mode", c_i32),
-                ("deterministic", c_i32)]
+                ("deterministic", c_i32), ("cent_obs", c_vp)]
 
 
 class MappoBwdArgs(ctypes.Structure):
@@ -323,7 +323,7 @@ class MappoBwdArgs(ctypes.Structure):
                 ("active", c_vp), ("act", c_vp), ("adv", c_vp), ("old_logp", c_vp), ("old_value", c_vp),
                 ("returns", c_vp), ("stats", c_vp), ("loss_acc", c_vp), ("clip", c_f32), ("huber_delta", c_f32),
                 ("entropy_coef", c_f32), ("value_coef", c_f32), ("en", c_i64), ("T", c_i32), ("L", c_i32),
-                ("rs", c_i64)]
+                ("rs", c_i64), ("cent_obs", c_vp)]
 
 
 _MD = ctypes.POINTER(MappoDims)

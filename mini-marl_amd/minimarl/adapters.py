@@ -245,21 +245,36 @@ class Target_Double_Dqn(Target_Dqn):
 
 
 class R_MAPPOPolicy:
-    """rmappo_policy.py:7-153 over the fused actor / critic kernels (shared policy, recurrent, Discrete)."""
+    """rmappo_policy.py:7-153 over the fused actor / critic kernels (shared policy, recurrent, Discrete).
+
+    args.use_centralized_V with cent_obs_space.shape == (n * D,): the critic reads the explicit cent_obs the
+    caller passes (share_obs, base_runner.py:155-161), as in the reference's signatures."""
 
     def __init__(self, args, obs_space, cent_obs_space, act_space, device="cuda", seed=None):
         from .mappo import MappoPolicy
         self.device = torch.device(device)
         D = int(obs_space.shape[0])
+        cent_agents = None
         if tuple(cent_obs_space.shape) != tuple(obs_space.shape):
-            raise NotImplementedError("use_centralized_V=True (critic input != actor input) is not on the hot "
-                                      "path (mappo/_config.py:146-150 default False)")
+            if not getattr(args, "use_centralized_V", False):
+                raise NotImplementedError("use_centralized_V=True (critic input != actor input) is not on the hot "
+                                          "path (mappo/_config.py:146-150 default False)")
+            Dc = int(cent_obs_space.shape[0])
+            if len(cent_obs_space.shape) != 1 or Dc % D or Dc // D < 2:
+                raise ValueError(f"cent_obs_space {tuple(cent_obs_space.shape)} is not n x obs_space ({D},)")
+            cent_agents = Dc // D
         self.hidden = int(getattr(args, "hidden_size", 32))
         self.actor_lr = float(getattr(args, "actor_lr", getattr(args, "lr", 1e-4)))
         self.critic_lr = float(getattr(args, "critic_lr", 1e-4))
         self.opti_eps = float(getattr(args, "opti_eps", 1e-5))
-        self.policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device, seed=seed)
+        self.policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device, seed=seed, cent_agents=cent_agents)
         self.actor, self.critic = self.policy.actor, self.policy.critic
+        self.cent_agents = cent_agents
+        # evaluate_actions' actor half runs the decentralized TRAIN forward (both nets; its critic's values are
+        # dropped): a decentralized policy whose actor storage is pointed at self.policy's on every call
+        self._actor_policy = self.policy
+        if cent_agents:
+            self._actor_policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device)
         self.seed = int(getattr(args, "seed", 1))
         self._counter = 0
         self._eval = {}
@@ -268,6 +283,12 @@ class R_MAPPOPolicy:
         return _dev(x, self.device).contiguous()
 
     def _same_input(self, obs, cent_obs):
+        """The explicit critic input of a centralized policy, None for a decentralized one (cent_obs == obs)."""
+        if self.cent_agents:
+            co = self._t(cent_obs)
+            if co.shape[0] != obs.shape[0] or co.shape[-1] != self.policy.Dc:
+                raise ValueError(f"cent_obs {tuple(co.shape)}: expected [{obs.shape[0]}, {self.policy.Dc}]")
+            return co
         if cent_obs is obs:
             return
         co = self._t(cent_obs)
@@ -277,12 +298,13 @@ class R_MAPPOPolicy:
     def get_actions(self, obs, cent_obs, rnn_states_actor, rnn_states_critic, masks, available_actions=None,
                     deterministic=False):
         obs_t = self._t(obs)
-        self._same_input(obs_t, cent_obs)
+        co = self._same_input(obs_t, cent_obs)
         R = obs_t.shape[0]
         ha = self._t(rnn_states_actor).reshape(R, self.hidden)
         hc = self._t(rnn_states_critic).reshape(R, self.hidden)
         m = self._t(masks).reshape(R)
-        v, a, lp, ha2, hc2 = self.policy.get_actions(obs_t, ha, hc, m, seed=self.seed, counter=self._counter)
+        v, a, lp, ha2, hc2 = self.policy.get_actions(obs_t, ha, hc, m, seed=self.seed, counter=self._counter,
+                                                     cent_obs=co)
         self._counter += 1
         return v, a.long(), lp, ha2.view(R, 1, self.hidden), hc2.view(R, 1, self.hidden)
 
@@ -300,8 +322,10 @@ class R_MAPPOPolicy:
         ha2, hc2 = torch.empty_like(ha), torch.empty_like(ha)
         lp, v = torch.empty(R, device=self.device), torch.empty(R, device=self.device)
         act = torch.empty(R, dtype=torch.int32, device=self.device)
+        # (the rollout launch runs both nets; a centralized critic gets a zero cent_obs, its value is dropped)
+        co = torch.zeros(R, self.policy.Dc, device=self.device) if self.cent_agents else None
         a = self.policy.rollout_args(obs_t, ha, hc, self._t(masks).reshape(R), ha2, hc2, lp, v, act_out=act,
-                                     seed=self.seed, counter=self._counter)
+                                     seed=self.seed, counter=self._counter, cent_obs=co)
         a.mode = MM_MAPPO_ROLLOUT
         a.deterministic = 1 if deterministic else 0
         self._counter += 1
@@ -312,10 +336,12 @@ class R_MAPPOPolicy:
                          available_actions=None, active_masks=None):
         """A minibatch of n recurrent chunks of length L (rows ordered (l, j), chunk-start hiddens [n, 1, H],
         shared_buffer.py:318-427) through the TRAIN-mode fused forward: values [L*n, 1], log-probs of
-        ``action`` [L*n, 1], entropy (masked mean over active_masks, r_actor_critic.py:95-140)."""
+        ``action`` [L*n, 1], entropy (masked mean over active_masks, r_actor_critic.py:95-140).
+        Centralized critic: the actor half as above; the values from L chained VALUES-mode forwards over the
+        explicit cent_obs (hidden carried from step to step, h <- h * mask inside the kernel)."""
         from .mappo import MappoBuffer, MappoTrainer
         obs_t = self._t(obs)
-        self._same_input(obs_t, cent_obs)
+        co = self._same_input(obs_t, cent_obs)
         rows = obs_t.shape[0]
         ha0 = self._t(rnn_states_actor)
         n = ha0.shape[0]
@@ -324,13 +350,15 @@ class R_MAPPOPolicy:
         key = (L, n)
         if key not in self._eval:
             buf = MappoBuffer(L, n, 1, self.policy.D, self.hidden, self.device)
-            self._eval[key] = (buf, MappoTrainer(self.policy, L, n, L=L, ppo_epoch=1, fused=False))
+            self._eval[key] = (buf, MappoTrainer(self._actor_policy, L, n, L=L, ppo_epoch=1, fused=False))
         buf, tr = self._eval[key]
+        if self.cent_agents:   # (looked up now: policy.actor.flat may have been rebound since construction)
+            self._actor_policy.actor.flat = self.policy.actor.flat
         buf.obs[:L].copy_(obs_t.view(L, n, -1))
         buf.masks[:L].copy_(self._t(masks).view(L, n))
         buf.rnn_states[0].copy_(ha0.reshape(n, self.hidden))
         buf.rnn_states_critic[0].copy_(self._t(rnn_states_critic).reshape(n, self.hidden))
-        d = ctypes.byref(self.policy.dims)
+        d = ctypes.byref(self._actor_policy.dims)
         check(lib().mm_mappo_fwd(d, ctypes.byref(tr.fwd_args(buf)), stream_handle(self.device)), "mappo_fwd(train)")
         A = self.policy.A
         ns0 = lib().mm_mappo_save_fields(d, 0)
@@ -338,6 +366,15 @@ class R_MAPPOPolicy:
         s0 = tr.save[0].view(-1, ns0, 64)
         logp_all = s0[:, ns0 - A:, :].permute(0, 2, 1).reshape(-1, A)[:rows]
         values = tr.save[1].view(-1, ns1, 64)[:, ns1 - 1, :].reshape(-1)[:rows]
+        if co is not None:
+            m_t = self._t(masks).view(L, n)
+            h = self._t(rnn_states_critic).reshape(n, self.hidden)
+            vs = []
+            for l in range(L):
+                h2 = torch.empty_like(h)
+                vs.append(self.policy.get_values(co[l * n:(l + 1) * n], h, m_t[l], hc_out=h2))
+                h = h2
+            values = torch.cat(vs, 0)
         act = self._t(action).reshape(rows, 1).long()
         lp = logp_all.gather(1, act)
         ent = -(logp_all.exp() * logp_all).sum(-1, keepdim=True)

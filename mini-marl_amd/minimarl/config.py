@@ -106,6 +106,8 @@ class MappoTrainConfig:
     gamma: float = 0.99
     gae_lambda: float = 0.95
     seed: int = 1
+    # centralized critic over the env's share_obs (mappo/_config.py use_centralized_V; MappoPolicy(cent_agents=n_agents))
+    use_centralized_V: bool = False
 
 
 @dataclass

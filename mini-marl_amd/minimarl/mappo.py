@@ -43,13 +43,18 @@ def ref_name(key, net):
 
 
 class MappoNet:
-    """One net's parameters (net 0 = R_Actor, net 1 = R_Critic) in the kernel's flat layout."""
+    """One net's parameters (net 0 = R_Actor, net 1 = R_Critic) in the kernel's flat layout.
 
-    def __init__(self, net, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None):
-        self.net, self.D, self.A, self.H = int(net), int(obs_dim), int(n_actions), int(hidden)
+    cent_agents n >= 2 (use_centralized_V): the critic's input is the env's share_obs, n obs rows wide; ``D`` is
+    the net's own input width (the critic's n * obs_dim), ``dims`` keeps the per-agent obs_dim."""
+
+    def __init__(self, net, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None):
+        self.net, self.A, self.H = int(net), int(n_actions), int(hidden)
+        self.cent_agents = int(cent_agents) if cent_agents and int(cent_agents) > 1 else None
+        self.D = int(obs_dim) * (self.cent_agents if self.cent_agents and self.net == 1 else 1)
         self.O = self.A if self.net == 0 else 1
         self.device = torch.device(device)
-        self.dims = MappoDims(self.D, self.H, self.A)
+        self.dims = MappoDims(int(obs_dim), self.H, self.A, self.cent_agents or 0)
         offs = (c_i64 * 19)()
         check(lib().mm_mappo_param_offsets(ctypes.byref(self.dims), self.net, offs), "mappo_param_offsets")
         self.offs = list(offs)
@@ -109,20 +114,39 @@ def _ptrs(*ts):
 class MappoPolicy:
     """R_MAPPOPolicy (rmappo_policy.py:7-153): shared actor + critic for all agents."""
 
-    def __init__(self, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None):
-        self.actor = MappoNet(0, obs_dim, n_actions, hidden, device, None if seed is None else seed)
-        self.critic = MappoNet(1, obs_dim, n_actions, hidden, device, None if seed is None else seed + 1)
+    def __init__(self, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None):
+        """cent_agents = n (use_centralized_V, base_runner.py:70-85): the critic reads the env's share_obs, the
+        concatenation of its n agents' obs rows (input width n * obs_dim); None: the row's own obs."""
+        self.actor = MappoNet(0, obs_dim, n_actions, hidden, device, None if seed is None else seed, cent_agents)
+        self.critic = MappoNet(1, obs_dim, n_actions, hidden, device, None if seed is None else seed + 1,
+                               cent_agents)
         self.dims = self.actor.dims
         self.D, self.A, self.H = int(obs_dim), int(n_actions), int(hidden)
+        self.cent_agents = self.actor.cent_agents
+        self.Dc = self.critic.D
         self.device = self.actor.device
+
+    def _critic_input(self, x):
+        """(obs, cent_obs) pointers' tensors for the critic from either form of its input: [R, D] rows grouped by
+        env (the n rows of an env adjacent: the critic gathers its share_obs from them) or explicit [R, n*D]."""
+        x = x.contiguous()
+        if self.cent_agents is None or x.shape[-1] == self.D:
+            if x.shape[-1] != self.D:
+                raise ValueError(f"critic input width {x.shape[-1]} != obs_dim {self.D}")
+            return x, None
+        if x.shape[-1] != self.Dc:
+            raise ValueError(f"critic input width {x.shape[-1]}: expected {self.D} (rows grouped by env) or "
+                             f"{self.Dc} (explicit cent_obs, {self.cent_agents} agents x {self.D})")
+        return None, x
 
     def _fwd(self, args):
         check(lib().mm_mappo_fwd(ctypes.byref(self.dims), ctypes.byref(args), stream_handle(self.device)),
               "mappo_fwd")
 
     def rollout_args(self, obs, ha, hc, masks, ha_out, hc_out, logp_out, value_out, act_out=None, act_in=None,
-                     u=None, seed=0, counter=0, counter_ptr=None):
+                     u=None, seed=0, counter=0, counter_ptr=None, cent_obs=None):
         a = MappoFwdArgs()
+        a.cent_obs = None if cent_obs is None else ptr(cent_obs)
         a.net[0].P, a.net[0].h_in, a.net[0].h_out, a.net[0].out = _ptrs(self.actor.flat, ha, ha_out, logp_out)
         a.net[1].P, a.net[1].h_in, a.net[1].h_out, a.net[1].out = _ptrs(self.critic.flat, hc, hc_out, value_out)
         a.obs, a.mask, a.act_in, a.act_out, a.u = _ptrs(obs, masks, act_in, act_out, u)
@@ -131,8 +155,11 @@ class MappoPolicy:
         a.mode = MM_MAPPO_ROLLOUT
         return a
 
-    def get_actions(self, obs, ha, hc, masks=None, actions=None, u=None, seed=0, counter=0):
+    def get_actions(self, obs, ha, hc, masks=None, actions=None, u=None, seed=0, counter=0, cent_obs=None):
         """obs [R,D], ha/hc [R,H], masks [R] -> values [R,1], actions [R,1], logp [R,1], ha', hc'.
+
+        Centralized critic: cent_obs [R, n*D] is the reference's explicit critic input; None reads the share_obs
+        from obs itself (rows grouped by env, R a multiple of n).
 
         The sample is drawn by the device RNG (or from injected uniforms u [R]); pass ``actions``
         to evaluate given actions (the reference's get_actions always samples, rmappo_policy.py:86)."""
@@ -142,17 +169,25 @@ class MappoPolicy:
         lp, v = torch.empty(R, device=dev), torch.empty(R, device=dev)
         act_in = None if actions is None else actions.reshape(-1).to(torch.int32).contiguous()
         act = torch.empty(R, dtype=torch.int32, device=dev) if actions is None else act_in
+        if cent_obs is not None:
+            cent_obs = self._critic_input(cent_obs)[1]
         self._fwd(self.rollout_args(obs.contiguous(), ha.contiguous(), hc.contiguous(),
                                     None if masks is None else masks.reshape(-1).contiguous(), ha2, hc2, lp, v,
-                                    None if actions is not None else act, act_in, u, seed, counter))
+                                    None if actions is not None else act, act_in, u, seed, counter,
+                                    cent_obs=cent_obs))
         return v.view(R, 1), act.view(R, 1), lp.view(R, 1), ha2, hc2
 
-    def get_values(self, obs, hc, masks=None):
+    def get_values(self, obs, hc, masks=None, hc_out=None):
+        """obs: the critic's input, [R, D] (centralized: rows grouped by env) or an explicit cent_obs [R, n*D];
+        hc_out [R, H] (optional) receives the critic's new hidden."""
         R = obs.shape[0]
         v = torch.empty(R, device=self.device)
         a = MappoFwdArgs()
-        a.net[1].P, a.net[1].h_in, a.net[1].out = _ptrs(self.critic.flat, hc.contiguous(), v)
-        a.obs, a.mask = _ptrs(obs.contiguous(), None if masks is None else masks.reshape(-1).contiguous())
+        a.net[1].P, a.net[1].h_in, a.net[1].out, a.net[1].h_out = _ptrs(self.critic.flat, hc.contiguous(), v, hc_out)
+        o, co = self._critic_input(obs)
+        # (the kernel's obs pointer is required; with an explicit cent_obs the critic does not read it)
+        a.obs, a.cent_obs, a.mask = _ptrs(co if o is None else o, co,
+                                          None if masks is None else masks.reshape(-1).contiguous())
         a.rows, a.mode = R, MM_MAPPO_VALUES
         self._fwd(a)
         return v.view(R, 1)
@@ -219,6 +254,13 @@ class MappoTrainer:
         kernel writing per-row operands and the separate weight-gradient reduction."""
         assert T % L == 0, "episode length must be a multiple of data_chunk_length"
         self.fused = bool(fused)
+        if not self.fused and policy.cent_agents:
+            raise NotImplementedError(f"fused=False does not support a centralized critic (cent_agents="
+                                      f"{policy.cent_agents}, critic input width {policy.Dc}): only the fused "
+                                      "gradient pass (mm_mappo_grad) reads share_obs")
+        if policy.cent_agents and int(EN) % policy.cent_agents:
+            raise ValueError(f"EN={EN} is not a multiple of cent_agents={policy.cent_agents} (rows of an env must be "
+                             "adjacent)")
         self.p = policy
         self.T, self.EN, self.L, self.epochs = int(T), int(EN), int(L), int(ppo_epoch)
         self.clip, self.huber, self.ent, self.vcoef = clip_param, huber_delta, entropy_coef, value_loss_coef
@@ -262,6 +304,17 @@ class MappoTrainer:
 
     def restore_tensors(self, ts, scalars):
         from .checkpoint import copy_into
+        if tuple(ts["critic"].shape) != tuple(self.p.critic.flat.shape):
+            # (centralized vs decentralized critic: name the widths, not the flat parameter counts)
+            c, H = self.p.critic, self.p.H
+            # total = (H + 2) * ceil4(Din) + the width-independent rest
+            rest = c.total - (H + 2) * c.Dp
+            dp, rem = divmod(int(ts["critic"].numel()) - rest, H + 2)
+            if rem or dp <= 0 or ts["critic"].dim() != 1:   # not an input-width difference: the plain shape error
+                copy_into(self.p.critic.flat, ts["critic"], "critic")
+            raise ValueError(f"checkpoint critic input width {dp} (padded to 4) != this trainer's critic input width "
+                             f"{c.D} (obs_dim {self.p.D}, cent_agents {self.p.cent_agents}): a decentralized and a "
+                             "centralized critic (use_centralized_V) are not interchangeable")
         copy_into(self.p.actor.flat, ts["actor"], "actor")
         copy_into(self.p.critic.flat, ts["critic"], "critic")
         copy_into(self.vn, ts["vn"], "vn")
@@ -380,6 +433,8 @@ class MappoRunner:
     def __init__(self, env, policy, T=100, L=5, ppo_epoch=15, gamma=0.99, gae_lambda=0.95, seed=0,
                  grad_allreduce=None):
         self.env, self.p = env, policy
+        if policy.cent_agents not in (None, env.N):
+            raise ValueError(f"policy.cent_agents={policy.cent_agents} != the env's {env.N} agents")
         self.E, self.N, self.D = env.E, env.N, env.obs_dim
         self.T, self.gamma, self.gl = int(T), gamma, gae_lambda
         dev = self.device = policy.device

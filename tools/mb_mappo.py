@@ -1,7 +1,8 @@
 """MAPPO phase timing at BASELINE config 3 (4096 envs x 8 agents, T=100, L=5, 15 PPO epochs).
 
-usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n]
-Prints one JSON line: ms per rollout step, per compute (values + GAE), per train() and per epoch.
+usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n] [--centralized-v]
+Prints one JSON line: ms per rollout step, per compute (values + GAE), per train() and per epoch (medians over the
+timed episodes; the first episode is warm-up). --centralized-v: the critic reads the env's share_obs.
 """
 import argparse
 import json
@@ -25,9 +26,10 @@ def main():
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--epochs", type=int, default=15)
     ap.add_argument("--episodes", type=int, default=2)
+    ap.add_argument("--centralized-v", action="store_true", help="centralized critic (use_centralized_V)")
     a = ap.parse_args()
     env = VecEnv(a.envs, a.agents, max_steps=100, device="cuda")
-    p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0)
+    p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0, **({"cent_agents": a.agents} if a.centralized_v else {}))
     r = MappoRunner(env, p, T=a.T, L=5, ppo_epoch=a.epochs, seed=1)
     r.warmup()
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -44,13 +46,14 @@ def main():
         torch.cuda.synchronize()
         if ep > 0:
             res.append((e0.elapsed_time(e1), e1.elapsed_time(e2), e2.elapsed_time(e3)))
-    ro = sum(x[0] for x in res) / len(res)
-    co = sum(x[1] for x in res) / len(res)
-    tr = sum(x[2] for x in res) / len(res)
+    med = lambda v: sorted(v)[len(v) // 2] if len(v) % 2 else sum(sorted(v)[len(v) // 2 - 1:len(v) // 2 + 1]) / 2
+    ro, co, tr = (med([x[i] for x in res]) for i in range(3))
+    epi = med([sum(x) for x in res])   # (the median episode, not the sum of the phase medians)
     rows = a.envs * a.agents * a.T
-    out = {"envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs,
+    out = {"envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs, "centralized_v": bool(a.centralized_v),
+           "episodes": len(res),
            "rollout_ms_per_step": ro / a.T, "compute_ms": co, "train_ms": tr, "train_ms_per_epoch": tr / a.epochs,
-           "episode_ms": ro + co + tr, "agent_env_steps_per_s_incl_train": rows / ((ro + co + tr) / 1e3),
+           "episode_ms": epi, "agent_env_steps_per_s_incl_train": rows / (epi / 1e3),
            "rollout_agent_env_steps_per_s": rows / (ro / 1e3), "train_info": {k: float(v) for k, v in info.items()}}
     print(json.dumps(out))
 
