@@ -15,11 +15,13 @@
 // Arithmetic: exact-f32 MFMA v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "env_dev.h"
 #include "minimarl.h"
 #include "qnet_geo.h"
+#include "rollout_env.h"
 
 namespace mm {
 
@@ -1055,9 +1057,6 @@ __global__ __launch_bounds__(256, (F1 > 64 ? 1 : 2)) void agent_q_fwd_kernel(QFw
 // [16-row half q][part hi|lo][lane][8 halves] = 4 KiB, every A fragment one conflict-free
 // ds_read_b128 (lane (i, g) of half q holds W[32rb + 16q + i][32kb + kperm16(j, g)]); biases in
 // natural order.
-#ifndef MM_H3_LB
-#define MM_H3_LB 1
-#endif
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1072,13 +1071,9 @@ __device__ __forceinline__ f32x4 mfma16x16(const f16x8& a, const f16x8& b, f32x4
 struct KS {
   f16x8 h, l;
 };
-#ifndef MM_SPLIT_MIX
-#define MM_SPLIT_MIX 1
-#endif
 typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
 typedef float f32x2_ __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split8(const float (&x)[8], KS& t, int lo_pairs = 4) {
-#if MM_SPLIT_MIX
   // per pair: hi = v_cvt_pk_f16_f32 (round to nearest even, as (_Float16)x), lo = f16(x - hi) by v_fma_mixlo / mixhi
   // (fma(hi, -1, x) with hi read as f16 and x as f32: the residual x - hi is exact in f32, rounded once to f16 — the
   // same bits as (_Float16)(x - (float)hi)); 3 VALU per pair instead of ~5.5
@@ -1098,14 +1093,6 @@ __device__ __forceinline__ void split8(const float (&x)[8], KS& t, int lo_pairs 
   }
   t.h = __builtin_bit_cast(f16x8, hw);
   t.l = __builtin_bit_cast(f16x8, lw);
-#else
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 hv = (_Float16)x[j];
-    t.h[j] = hv;
-    t.l[j] = (_Float16)(x[j] - (float)hv);
-  }
-#endif
 }
 // two consecutive 16-row D tiles -> one k-step
 __device__ __forceinline__ void split_pair(const f32x4& a, const f32x4& b, KS& t) {
@@ -1203,10 +1190,7 @@ __device__ __forceinline__ int q_epilogue16(const QFwdParams& p, int agent, int 
   }
   int act = bi;
   if (io.mode == MM_Q_ACT) {
-#ifndef MM_RNG_SPLIT
-#define MM_RNG_SPLIT 1
-#endif
-    if (MM_RNG_SPLIT && !io.u && !io.rand_act) {
+    if (!io.u && !io.rand_act) {
       // both device draws of env c in ONE rng_draw sequence: lanes of even g draw the uniform, odd g the random
       // action (the same (seed, counter, e, b) streams as two calls), exchanged across g by an xor-16 shuffle
       const bool ra_lane = (g & 1) != 0;
@@ -1271,16 +1255,13 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
   const bool valid = e < p.E;
   const mm_qfwd_io& io = p.io;
   const int ATr = (p.A + 15) / 16;   // Q tiles that hold real actions
-#ifndef MM_LDS_REBASE
-#define MM_LDS_REBASE 1
-#endif
   // LDS image addressing of the post-layer-1 fragments and the biases: per-lane base pointers every 15360 floats (each
   // 4 KiB block then lies within the 64 KiB immediate offset of its base) and one for the biases (+ 4 g), made opaque in
   // the LDS address space, so each ds_read_b128 is base + immediate (no v_add per fragment beyond the first 64 KiB)
   constexpr int NWB = (CG::off_b1 + 15359) / 15360;
   auto lds_opaque = [](const float* q) {
     auto l = (const __attribute__((address_space(3))) float*)q;
-    if (MM_LDS_REBASE) asm volatile("" : "+v"(l));
+    asm volatile("" : "+v"(l));
     return (const float*)l;
   };
   const float* WL[NWB];
@@ -1393,10 +1374,6 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
     for (int kb = 0; kb < RB2; ++kb) tri(CG::off_ih + (rb * RB2 + kb) * 1024, HB * RB2 * 1024, x2s[kb], ar, az, anx);
 #pragma unroll
     for (int kb = 0; kb < HB; ++kb) tri(CG::off_hh + (rb * HB + kb) * 1024, HB * HB * 1024, h0s[kb], ar, az, anh);
-#ifndef MM_H3_PK
-#define MM_H3_PK 1
-#endif
-#if MM_H3_PK
     // gates two rows at a time on packed f32 (v_pk_mul / v_pk_add / v_pk_fma: two values per VALU
     // issue); the transcendentals stay scalar. Same operations as sigmoidf_ / tanhf_.
     float rrs[4], zs[4], ns[4];
@@ -1446,24 +1423,6 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
         o[5 * H] = h1[t][r];
       }
     }
-#else
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float rr = sigmoidf_(ar[r]);
-      const float z = sigmoidf_(az[r]);
-      const float n = tanhf_(anx[r] + rr * anh[r]);
-      h1[t][r] = n + z * (h0[t][r] - n);
-      if (sv) {
-        float* o = sv + F1 + G + 16 * t + 4 * g + r;
-        o[0] = h0[t][r];
-        o[H] = rr;
-        o[2 * H] = z;
-        o[3 * H] = n;
-        o[4 * H] = anh[r];
-        o[5 * H] = h1[t][r];
-      }
-    }
-#endif
     if (hop) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) hop[(int64_t)(16 * t + r) * io.hout_sf] = h1[t][r];
@@ -1490,11 +1449,36 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
   return q_epilogue16<AT>(p, agent, e, valid, qa, eps, ctr, out_off, rng_in);
 }
 
+// ---- prologue pieces shared by the 1024-thread kernels (one agent's image in LDS per block)
+// range guard (qnet_h3_bound_block): an agent whose split operands could leave the f16 range runs on the exact-f32 image
+__device__ __forceinline__ bool agent_range_guarded(const QFwdParams& p, int agent) {
+  return reinterpret_cast<const int*>(p.packed + 2 * p.g.agent_stride * p.N)[agent] != 0;
+}
+// the agent's weight image: the exact-f32 one (first N images of packed), or the fp16x3 one (the next N)
+__device__ __forceinline__ const float* agent_image_src(const QFwdParams& p, int agent, bool exact) {
+  return p.packed + (exact ? 0 : (int64_t)p.N * p.g.agent_stride) + (int64_t)agent * p.g.agent_stride;
+}
+// LDS-DMA of an image of nchunk 1 KiB pieces into wsm by waves first_wave .. first_wave + n_waves - 1 of the block
+__device__ __forceinline__ void image_dma(const float* src, float* wsm, int nchunk, int first_wave, int n_waves) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (wave >= first_wave)
+    for (int c = wave - first_wave; c < nchunk; c += n_waves) glds_dwordx4(src + c * 256 + lane * 4, wsm + c * 256);
+}
+// the fp16x3 body's hidden-state tiles of lane (env ec, g): features 16 t + 4 g + r
+template <int H>
+__device__ __forceinline__ void load_h0(const mm_qfwd_io& io, int ec, int agent, int g, f32x4 (&h0)[H / 16]) {
+  const float* hp = io.h_in + (int64_t)ec * io.hin_se + (int64_t)agent * io.hin_sa + (int64_t)(4 * g) * io.hin_sf;
+#pragma unroll
+  for (int t = 0; t < H / 16; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h0[t][r] = hp[(int64_t)(16 * t + r) * io.hin_sf];
+}
+
 // The LDS-staged large-E kernel on the fp16x3 image: a 1024-thread block (16 waves x 16 envs = 256
 // envs of one agent) first DMAs the agent's image into LDS (global_load_lds_dwordx4, issued after
 // every global read of the wave so the latencies overlap), then runs the body. One block per CU.
 template <int F1, int G, int H, int AB>
-__global__ __launch_bounds__(1024, MM_H3_LB) void agent_q_fwd_h3_kernel(QFwdParams p0, QFwdParams p1) {
+__global__ __launch_bounds__(1024, 1) void agent_q_fwd_h3_kernel(QFwdParams p0, QFwdParams p1) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];
   const bool second = (int)blockIdx.x >= p0.nblocks;
   // the selected net's parameters read straight from the kernarg segment (p0, p1 back to back):
@@ -1508,13 +1492,11 @@ __global__ __launch_bounds__(1024, MM_H3_LB) void agent_q_fwd_h3_kernel(QFwdPara
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // range guard (qnet_h3_bound_block): an agent whose split operands could leave the f16 range runs
   // this block on the exact-f32 image (8 waves x 32 envs = the same 256 envs), the rest idle
-  if (reinterpret_cast<const int*>(p.packed + 2 * p.g.agent_stride * p.N)[agent]) {
+  if (agent_range_guarded(p, agent)) {
     const int e32 = tile * 256 + wave * 32 + (lane & 31);
-    const float* src32 = p.packed + (int64_t)agent * p.g.agent_stride;
+    const float* src32 = agent_image_src(p, agent, true);
     const int nch = (int)(p.g.agent_stride >> 8);
-    for (int c = wave; c < nch; c += 16)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src32 + c * 256 + lane * 4),
-                                       (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
+    for (int c = wave; c < nch; c += 16) glds_dwordx4(src32 + c * 256 + lane * 4, wsm + c * 256);
     const float* orow32 = obs_row_ptr(p, agent, e32);
     float x32[16];
     load_obs_kblock(orow32, 0, p.D, x32);
@@ -1531,20 +1513,15 @@ __global__ __launch_bounds__(1024, MM_H3_LB) void agent_q_fwd_h3_kernel(QFwdPara
   // weight image DMA first (no dependencies), then the wave's own global reads: the hidden state
   // (independent of the reset flag: loaded unconditionally, zeroed after), the obs row index and
   // the obs k-step 0 that depends on it. All latencies overlap before the barrier.
-  const float* src = p.packed + (int64_t)p.N * p.g.agent_stride + (int64_t)agent * p.g.agent_stride;
+  // (the DMA loop stays written out in this kernel: through image_dma two instantiations spill more)
+  const float* src = agent_image_src(p, agent, false);
   const int nchunk = (int)(p.g.agent_stride >> 8);
-  for (int c = wave; c < nchunk; c += 16)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                     (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
+  for (int c = wave; c < nchunk; c += 16) glds_dwordx4(src + c * 256 + lane * 4, wsm + c * 256);
   const mm_qfwd_io& io = p.io;
   const int ec = min(e, p.E - 1);
   f32x4 h0[H / 16];
   if (io.h_in) {
-    const float* hp = io.h_in + (int64_t)ec * io.hin_se + (int64_t)agent * io.hin_sa + (int64_t)(4 * g) * io.hin_sf;
-#pragma unroll
-    for (int t = 0; t < H / 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h0[t][r] = hp[(int64_t)(16 * t + r) * io.hin_sf];
+    load_h0<H>(io, ec, agent, g, h0);
   } else {
 #pragma unroll
     for (int t = 0; t < H / 16; ++t) h0[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1632,104 +1609,6 @@ static_assert(sizeof(QFwdParams) % 8 == 0 && alignof(RollStep) == 8, "rollout_st
 #else
 #define MM_ROLL_PROBE 0
 #endif
-static constexpr int kRollMaxN = 10;    // 3 ceil(N / 2) <= 16 rows and agent markers 3 + k in a nibble
-static constexpr int kRollMaxR = 16;    // rows of 8 cells: one 32-bit nibble word per row
-
-// LDS staging of the env step (after the weight image): coordinate features, the tile's grids as nibble rows
-// (row r of env l = cells (r, 0..7) at bits 4c of word l * roll_gbw(R) + r), agent cells r << 4 | c, done flags
-struct RollLds {
-  int stab, sgrid, spos, sdone, total;
-};
-__host__ __device__ __forceinline__ int roll_gbw(int R) { return R | 1; }   // odd word stride: fewer bank conflicts
-__host__ __device__ __forceinline__ RollLds roll_lds(int R, int C, int N) {
-  auto a16 = [](int x) { return (x + 15) & ~15; };
-  RollLds m;
-  int o = 0;
-  m.stab = o;  o = a16(o + (R + C) * 4);
-  m.sgrid = o; o = a16(o + 256 * roll_gbw(R) * 4);
-  m.spos = o;  o = a16(o + 256 * N);
-  m.sdone = o; o = a16(o + 256);
-  m.total = o;
-  return m;
-}
-// 4 grid bytes (codes < 16) -> 4 nibbles, and back
-__device__ __forceinline__ uint32_t nib_pack4(uint32_t x) {
-  return (x & 0xFu) | ((x >> 4) & 0xF0u) | ((x >> 8) & 0xF00u) | ((x >> 12) & 0xF000u);
-}
-__device__ __forceinline__ uint32_t nib_unpack4(uint32_t x) {
-  return (x & 0xFu) | ((x & 0xF0u) << 4) | ((x & 0xF00u) << 8) | ((x & 0xF000u) << 12);
-}
-// position word of the global state (prev_r << 24 | prev_c << 16 | r << 8 | c) -> 16 bits (4 per field)
-__device__ __forceinline__ uint32_t pos16(int32_t w) {
-  return (uint32_t)((((w >> 24) & 15) << 12) | (((w >> 16) & 15) << 8) | (((w >> 8) & 15) << 4) | (w & 15));
-}
-
-// The local observation of an agent at (r, c) as a bit word: bit f = feature f (>= 2) of get_agent_obs, i.e. bit
-// 2 + 5 cell + ch for the 3 x 3 cells (row-major) x {lemon, apple, even agent, odd agent, wall}; off-grid cells
-// are 0 (env.hip obs_value). Item code -> channel bits by a nibble table: 1 lemon, 2 apple, 3 + k agent k.
-__device__ __forceinline__ uint64_t roll_obs_word(const uint32_t* rows, int R, int r, int c) {
-  const uint32_t wm = r > 0 ? rows[r - 1] : 0u, w0 = rows[r], wp = r + 1 < R ? rows[r + 1] : 0u;
-  auto nb3 = [c](uint32_t w) { return (c > 0 ? (w >> (4 * c - 4)) : (w << 4)) & 0xFFFu; };   // cells c-1, c, c+1
-  const uint64_t items = (uint64_t)nb3(wm) | ((uint64_t)nb3(w0) << 12) | ((uint64_t)nb3(wp) << 24);
-  constexpr uint64_t kLut = 0x4848484848484210ull;   // item -> {lemon 1, apple 2, even agent 4, odd agent 8}
-  uint64_t word = 0;
-#pragma unroll
-  for (int cell = 0; cell < 9; ++cell) {
-    const uint32_t it = (uint32_t)(items >> (4 * cell)) & 15u;
-    word |= ((kLut >> (4 * it)) & 15ull) << (2 + 5 * cell);
-  }
-  return word;
-}
-// roll_obs_word shared by the 4 lanes (c, g = 0..3) of one env in the fp16x3 layout: lane group g < 3 builds the 3 cells
-// of grid row r - 1 + g (bits 2 + 15 g .. 16 + 15 g of the word), and two v_permlane16/32_swap ORs per dword combine
-// the groups (the 4 lanes of an env differ in lane bits 4 and 5) — the same word, one row read and ~1/3 of the ALU
-// per lane. Every lane of the wave must be active.
-__device__ __forceinline__ uint64_t roll_obs_word_g(const uint32_t* rows, int R, int r, int c, int g) {
-  const int rr = r - 1 + g;
-  const uint32_t w = (g < 3 && rr >= 0 && rr < R) ? rows[rr] : 0u;
-  const uint32_t f12 = (c > 0 ? (w >> (4 * c - 4)) : (w << 4)) & 0xFFFu;   // cells c-1, c, c+1
-  constexpr uint64_t kLut = 0x4848484848484210ull;   // item -> {lemon 1, apple 2, even agent 4, odd agent 8}
-  uint32_t f15 = 0;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const uint32_t it = (f12 >> (4 * j)) & 15u;
-    f15 |= (uint32_t)((kLut >> (4 * it)) & 15ull) << (5 * j);
-  }
-  uint32_t lo = g < 2 ? f15 << (2 + 15 * g) : 0u, hi = g == 2 ? f15 : 0u;
-  auto or16 = [](uint32_t v) {
-    const auto x = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return x[0] | x[1];
-  };
-  auto or32 = [](uint32_t v) {
-    const auto x = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return x[0] | x[1];
-  };
-  lo = or32(or16(lo));
-  hi = or32(or16(hi));
-  return ((uint64_t)hi << 32) | lo;
-}
-// features f0 .. f0 + 3 of the word into x[0..3] (the coordinates for f < 2)
-__device__ __forceinline__ void roll_feat4(uint64_t word, int f0, float cr, float cc, float* x) {
-  const uint32_t fld = f0 < 64 ? (uint32_t)(word >> f0) : 0u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = (float)((fld >> i) & 1u);
-  if (f0 == 0) {
-    x[0] = cr;
-    x[1] = cc;
-  }
-}
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-// store features f0 .. f0 + 3 (< D) of one (env, agent) row
-__device__ __forceinline__ void roll_store4(float* dst, int f0, int D, const float* x) {
-  if (f0 + 3 < D) {
-    *reinterpret_cast<f32x4u*>(dst + f0) = f32x4u{x[0], x[1], x[2], x[3]};
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (f0 + i < D) dst[f0 + i] = x[i];
-  }
-}
-
 template <int F1, int G, int H, int AB>
 __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QFwdParams p1, RollStep rs_) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];
@@ -1758,7 +1637,7 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
   const int e0 = tile * 256;
   const int par = rs.par;
   const mm_qfwd_io& io = p.io;
-  const bool exact = reinterpret_cast<const int*>(p.packed + 2 * p.g.agent_stride * p.N)[agent] != 0;
+  const bool exact = agent_range_guarded(p, agent);
   MM_RSTAMP(0, threadIdx.x == 0);
 
   if (threadIdx.x >= 256 && threadIdx.x < 256 + R + C) {
@@ -1872,13 +1751,7 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
         aq[k >> 3] |= (uint32_t)(ac[k] & 15) << (4 * (k & 7));
         spos[le_d * N + k] = (uint8_t)((pos_r(w) << 4) | pos_c(w));
       }
-#pragma unroll
-    for (int j = 0; j < kRollMaxR / 2; ++j)
-      if (2 * j < R) {   // 16 bytes = 2 rows of 8 cells (RC = 8 R)
-        const uint4 g = gin[j];
-        rows[2 * j] = nib_pack4(g.x) | (nib_pack4(g.y) << 16);
-        if (2 * j + 1 < R) rows[2 * j + 1] = nib_pack4(g.z) | (nib_pack4(g.w) << 16);
-      }
+    roll_unpack_rows(gin, rows, R);
   }
   // the store rows of this wave's envs (h3 lane mapping, and the exact path's 32-env mapping), read from the
   // staging before the image DMA overwrites it: no global round trip in front of the first obs store
@@ -1899,30 +1772,15 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
 #endif
   // ---- waves 4-15, once the env inputs have been consumed: the weight image DMA into the staging region
   // (range-guarded agents: the exact-f32 image) while waves 0-3 run the env step
-  if (wave >= 4) {
-    const float* src = p.packed + (exact ? 0 : (int64_t)p.N * p.g.agent_stride) + (int64_t)agent * p.g.agent_stride;
-    const int nchunk = (int)(p.g.agent_stride >> 8);
-    for (int c = wave - 4; c < nchunk; c += 12)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                       (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
-  }
+  image_dma(agent_image_src(p, agent, exact), wsm, (int)(p.g.agent_stride >> 8), 4, 12);
   const int le = wave * 16 + (lane & 15), e = e0 + le;
   if (rs.begin) {
     // chunk start: slot 0 of the staging rows <- s_t, the observation of the state before this step; lane
     // (env, g) writes features 16 q + 4 g .. + 3 of its env
     __syncthreads();
-    if (!second && e < E && srow_h3 >= 0) {
-      const int rc = spos[le * N + agent];
-      const uint64_t wd =
-          roll_obs_word(reinterpret_cast<const uint32_t*>(sgrid) + le * roll_gbw(R), R, rc >> 4, rc & 15);
-      const float cr = stab[rc >> 4], cc = stab[R + (rc & 15)];
-      float* d0 = rs.store_obs + srow_h3 * rs.row_stride + (int64_t)agent * D;
-      for (int f0 = 4 * (lane >> 4); f0 < D; f0 += 16) {
-        float x[4];
-        roll_feat4(wd, f0, cr, cc, x);
-        roll_store4(d0, f0, D, x);
-      }
-    }
+    if (!second && e < E && srow_h3 >= 0)
+      roll_store_slot0(reinterpret_cast<const uint32_t*>(sgrid) + le * roll_gbw(R), spos[le * N + agent], stab, R,
+                       rs.store_obs + srow_h3 * rs.row_stride + (int64_t)agent * D, D, lane >> 4);
     __syncthreads();
   }
   if (dvalid) {
@@ -1939,38 +1797,12 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
       pq[kRollMaxN / 2 - 1] >>= 16;
       aq[0] = __builtin_amdgcn_alignbit(aq[1], aq[0], 4);
       aq[1] >>= 4;
-      int r = (w >> 4) & 15, c = w & 15, pr = (w >> 12) & 15, pc = (w >> 8) & 15;
-      const int nr = r + (a == 0 ? 1 : (a == 2 ? -1 : 0));
-      const int nc = c + (a == 1 ? -1 : (a == 3 ? 1 : 0));
-      const bool inside = a != 4 && nr >= 0 && nr < R && nc >= 0 && nc < C;
-      // every row this agent may read or write, in one round trip: the target row, its own row, its stale prev row
-      const uint32_t w_n = rows[inside ? nr : r], w_r = rows[r], w_p = rows[pr];
-      asm volatile("" ::"v"(w_n), "v"(w_r), "v"(w_p));   // all three reads in flight together (not sunk into branches)
-      const bool moved = inside && ((w_n >> (4 * nc)) & 15u) < 3u;
-      if (moved) {
-        pr = r;
-        pc = c;
-        r = nr;
-        c = nc;
-      }
-      // view update (ma_gym __update_agent_view) when agent_pos != agent_prev_pos: empty at agent_prev_pos, the
-      // marker at agent_pos; the fruit under a moving agent is eaten. Branch-free: both rows are written back
-      // every agent (unchanged when there is no update; the (r, c) row last, so a shared row gets both edits).
-      const bool upd = r != pr || c != pc;
-      const uint32_t A = moved ? w_n : w_r;   // row of (r, c)
-      const uint32_t B = moved ? w_r : w_p;   // row of (pr, pc)
-      const uint32_t item = upd ? (A >> (4 * c)) & 15u : 0u;
-      const bool big = (k & 1) == 0;
-      const float rk = ev.step_cost + (item == 1u ? (big ? -10.0f : -1.0f) : (item == 2u ? (big ? 10.0f : 1.0f) : 0.0f));
-      apples -= item == 2u ? 1 : 0;
-      const uint32_t clr = upd ? ~(15u << (4 * pc)) : ~0u;
-      const uint32_t A1 = pr == r ? (A & clr) : A;
-      rows[pr] = B & clr;
-      rows[r] = upd ? ((A1 & ~(15u << (4 * c))) | ((uint32_t)(3 + k) << (4 * c))) : A1;
-      spos[le_d * N + k] = (uint8_t)((r << 4) | c);
+      const RollMove mv = roll_agent_step(w, a, k, rows, R, C, ev.step_cost);
+      apples -= mv.ate ? 1 : 0;
+      spos[le_d * N + k] = (uint8_t)mv.w;   // r << 4 | c
       if (writer) {
-        pout[k] = (pr << 24) | (pc << 16) | (r << 8) | c;
-        rout[k] = rk;
+        pout[k] = pos32_from16(mv.w);
+        rout[k] = mv.rew;
       }
     }
     const bool dn = steps >= ev.max_steps || apples == 0;
@@ -1981,21 +1813,8 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
       rs.cur_row[de] = dn ? -1 : myrow;
       (par ? ev.steps : ev.steps_alt)[de] = dn ? 0 : steps;
       (par ? ev.apples : ev.apples_alt)[de] = dn ? ev.init_apples : apples;
-      uint4* gout = reinterpret_cast<uint4*>((par ? ev.grid : ev.grid_alt) + (int64_t)de * RC);
-      const uint4* ig = reinterpret_cast<const uint4*>(ev.init_grid);
-#pragma unroll
-      for (int j = 0; j < kRollMaxR / 2; ++j)
-        if (2 * j < R) {
-          uint4 v;
-          if (dn) {
-            v = ig[j];
-          } else {
-            const uint32_t a0 = rows[2 * j], a1 = 2 * j + 1 < R ? rows[2 * j + 1] : 0u;
-            v = make_uint4(nib_unpack4(a0 & 0xFFFFu), nib_unpack4(a0 >> 16), nib_unpack4(a1 & 0xFFFFu),
-                           nib_unpack4(a1 >> 16));
-          }
-          gout[j] = v;
-        }
+      roll_pack_rows(reinterpret_cast<uint4*>((par ? ev.grid : ev.grid_alt) + (int64_t)de * RC), rows,
+                     reinterpret_cast<const uint4*>(ev.init_grid), dn, R);
       if (dn)
         for (int k = 0; k < N; ++k) pout[k] = ev.init_pos[k];
     }
@@ -2039,13 +1858,7 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
   const int ec = min(e, E - 1);
   const int g = lane >> 4;
   f32x4 h0[H / 16];
-  {
-    const float* hp = io.h_in + (int64_t)ec * io.hin_se + (int64_t)agent * io.hin_sa + (int64_t)(4 * g) * io.hin_sf;
-#pragma unroll
-    for (int t = 0; t < H / 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h0[t][r] = hp[(int64_t)(16 * t + r) * io.hin_sf];
-  }
+  load_h0<H>(io, ec, agent, g, h0);
   const bool rt = !second && io.reset && io.reset[ec];
   const float eps = (io.mode == MM_Q_ACT && io.eps_ptr) ? *io.eps_ptr : io.epsilon;
   const uint64_t ctr = (io.mode == MM_Q_ACT && io.counter_ptr) ? *io.counter_ptr : io.counter;
@@ -2145,25 +1958,6 @@ struct RollChunk {   // kernarg right after the two QFwdParams
 };
 static_assert(alignof(RollChunk) == 8, "rollout_chunk kernarg layout");
 static constexpr uint64_t kHandoffTimeout = 2000000;   // s_memrealtime ticks (100 MHz): 20 ms
-
-// LDS after the weight image: coordinate features, nibble-row grids, 16-bit position words (prev_r, prev_c, r, c),
-// dones by step parity, the behavior block's outgoing actions
-struct RollChunkLds {
-  int stab, sgrid, spq, ssa, sdone, shx, total;
-};
-__host__ __device__ __forceinline__ RollChunkLds roll_chunk_lds(int R, int C, int N) {
-  auto a16 = [](int x) { return (x + 15) & ~15; };
-  RollChunkLds m;
-  int o = 0;
-  m.stab = o;  o = a16(o + (R + C) * 4);
-  m.sgrid = o; o = a16(o + 256 * roll_gbw(R) * 4);
-  m.spq = o;   o = a16(o + 256 * N * 2);
-  m.ssa = o;   o = a16(o + 2 * 256 * 2);
-  m.sdone = o; o = a16(o + 2 * 256);
-  m.shx = o;   o = a16(o + N * 32 * 4);   // (exact body: the outgoing actions, 256 B; every block: the step's hand-off words)
-  m.total = o;
-  return m;
-}
 
 // per-launch constants of a chunk-kernel block (computed once, read by the step loop)
 struct ChunkCtx {
@@ -2330,14 +2124,7 @@ __device__ __forceinline__ void roll_chunk_steps() {
           if (k < N) aq[k >> 3] |= ((hl[k * 32] >> sh) & 15u) << (4 * (k & 7));
         // (2) auto-reset of an env that ended at step t - 1 (the initial grid / positions / counters)
         if (cx.sdone[prv * 256 + le_d]) {
-          const uint4* ig = reinterpret_cast<const uint4*>(ev.init_grid);
-#pragma unroll
-          for (int j = 0; j < kRollMaxR / 2; ++j)
-            if (2 * j < R) {
-              const uint4 g = ig[j];
-              rows[2 * j] = nib_pack4(g.x) | (nib_pack4(g.y) << 16);
-              if (2 * j + 1 < R) rows[2 * j + 1] = nib_pack4(g.z) | (nib_pack4(g.w) << 16);
-            }
+          roll_unpack_rows(reinterpret_cast<const uint4*>(ev.init_grid), rows, R);
           for (int k = 0; k < N; ++k) cx.spq[le_d * N + k] = (uint16_t)pos16(ev.init_pos[k]);
           cx.ssa[le_d] = 0;
           cx.ssa[256 + le_d] = (uint16_t)ev.init_apples;
@@ -2360,17 +2147,9 @@ __device__ __forceinline__ void roll_chunk_steps() {
       __syncthreads();
       if (!second && e < E) {
         const int64_t srb = stg[e];
-        if (srb >= 0 && srb < rc.n_rows) {
-          const int rcw = cx.spq[le * N + agent] & 0xFF;
-          const uint64_t wd = roll_obs_word(cx.sgrid + le * roll_gbw(R), R, rcw >> 4, rcw & 15);
-          const float cr = cx.stab[rcw >> 4], cc = cx.stab[R + (rcw & 15)];
-          float* d0 = rc.store_obs + srb * rc.row_stride + (int64_t)agent * D;
-          for (int f0 = 4 * (lane >> 4); f0 < D; f0 += 16) {
-            float x[4];
-            roll_feat4(wd, f0, cr, cc, x);
-            roll_store4(d0, f0, D, x);
-          }
-        }
+        if (srb >= 0 && srb < rc.n_rows)
+          roll_store_slot0(cx.sgrid + le * roll_gbw(R), cx.spq[le * N + agent] & 0xFF, cx.stab, R,
+                           rc.store_obs + srb * rc.row_stride + (int64_t)agent * D, D, lane >> 4);
       }
       __syncthreads();
     }
@@ -2395,40 +2174,17 @@ __device__ __forceinline__ void roll_chunk_steps() {
 #pragma unroll
       for (int k = 0; k < kRollMaxN; ++k) {
         if (k < N) {
-        const uint32_t w = pq[0] & 0xFFFFu;
-        const int a = (int)(aq[0] & 15u);
+          const uint32_t w = pq[0] & 0xFFFFu;
+          const int a = (int)(aq[0] & 15u);
 #pragma unroll
-        for (int j = 0; j < kRollMaxN / 2 - 1; ++j) pq[j] = __builtin_amdgcn_alignbit(pq[j + 1], pq[j], 16);
-        pq[kRollMaxN / 2 - 1] >>= 16;
-        aq[0] = __builtin_amdgcn_alignbit(aq[1], aq[0], 4);
-        aq[1] >>= 4;
-        int r = (w >> 4) & 15, cc = w & 15, pr = (w >> 12) & 15, pc = (w >> 8) & 15;
-        const int nr = r + (a == 0 ? 1 : (a == 2 ? -1 : 0));
-        const int nc = cc + (a == 1 ? -1 : (a == 3 ? 1 : 0));
-        const bool inside = a != 4 && nr >= 0 && nr < R && nc >= 0 && nc < C;
-        const uint32_t w_n = rows[inside ? nr : r], w_r = rows[r], w_p = rows[pr];
-        asm volatile("" ::"v"(w_n), "v"(w_r), "v"(w_p));
-        const bool moved = inside && ((w_n >> (4 * nc)) & 15u) < 3u;
-        if (moved) {
-          pr = r;
-          pc = cc;
-          r = nr;
-          cc = nc;
-        }
-        const bool upd = r != pr || cc != pc;
-        const uint32_t A = moved ? w_n : w_r;
-        const uint32_t B = moved ? w_r : w_p;
-        const uint32_t item = upd ? (A >> (4 * cc)) & 15u : 0u;
-        const bool big = (k & 1) == 0;
-        const float mag = big ? 10.0f : 1.0f;   // (selects, no branch: item 1 lemon -mag, 2 apple +mag)
-        const float rk = ev.step_cost + (item == 2u ? mag : (item == 1u ? -mag : 0.0f));
-        apples -= item == 2u ? 1 : 0;
-        const uint32_t clr = upd ? ~(15u << (4 * pc)) : ~0u;
-        const uint32_t A1 = pr == r ? (A & clr) : A;
-        rows[pr] = B & clr;
-        rows[r] = upd ? ((A1 & ~(15u << (4 * cc))) | ((uint32_t)(3 + k) << (4 * cc))) : A1;
-        cx.spq[le_d * N + k] = (uint16_t)((pr << 12) | (pc << 8) | (r << 4) | cc);
-        if (writer) rout[k] = rk;
+          for (int j = 0; j < kRollMaxN / 2 - 1; ++j) pq[j] = __builtin_amdgcn_alignbit(pq[j + 1], pq[j], 16);
+          pq[kRollMaxN / 2 - 1] >>= 16;
+          aq[0] = __builtin_amdgcn_alignbit(aq[1], aq[0], 4);
+          aq[1] >>= 4;
+          const RollMove mv = roll_agent_step(w, a, k, rows, R, C, ev.step_cost);
+          apples -= mv.ate ? 1 : 0;
+          cx.spq[le_d * N + k] = (uint16_t)mv.w;
+          if (writer) rout[k] = mv.rew;
         }
       }
       const bool dn = st >= ev.max_steps || apples == 0;
@@ -2478,11 +2234,7 @@ __device__ __forceinline__ void roll_chunk_steps() {
       const int g = lane >> 4;
       f32x4 h0[H / 16];
       if (i == 0) {
-        const float* hp = io.h_in + (int64_t)ec * io.hin_se + (int64_t)agent * io.hin_sa + (int64_t)(4 * g) * io.hin_sf;
-#pragma unroll
-        for (int t = 0; t < H / 16; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h0[t][r] = hp[(int64_t)(16 * t + r) * io.hin_sf];
+        load_h0<H>(io, ec, agent, g, h0);
       } else {
 #pragma unroll
         for (int t = 0; t < H / 16; ++t) h0[t] = hkeep[t];
@@ -2557,21 +2309,14 @@ __global__ __launch_bounds__(1024, 1) void rollout_chunk_kernel(QFwdParams p0, Q
   const ChunkCtx cx = chunk_ctx<F1, G, H, AB>(kargs);
   const int nb = (int)gridDim.x;
   const QFwdParams& p = kargs[cx.second ? 1 : 0];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const EnvDev& ev = rc.env;
   const int R = ev.R, C = ev.C, RC = R * C, E = p.E;
   const int agent = cx.agent, e0 = cx.e0;
-  const bool exact = reinterpret_cast<const int*>(p.packed + 2 * p.g.agent_stride * N)[agent] != 0;
+  const bool exact = agent_range_guarded(p, agent);
   const int par = *rc.envpar;
 
   // ---- once per launch: the weight image (the exact-f32 one for a range-guarded agent) into LDS
-  {
-    const float* src = p.packed + (exact ? 0 : (int64_t)N * p.g.agent_stride) + (int64_t)agent * p.g.agent_stride;
-    const int nchunk = (int)(p.g.agent_stride >> 8);
-    for (int c = wave; c < nchunk; c += 16)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                       (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
-  }
+  image_dma(agent_image_src(p, agent, exact), wsm, (int)(p.g.agent_stride >> 8), 0, 16);
   if (threadIdx.x >= 256 && threadIdx.x < 256 + R + C) {
     const int i = threadIdx.x - 256;
     cx.stab[i] = i < R ? ev.rtab[i] : ev.ctab[i - R];
@@ -2586,13 +2331,7 @@ __global__ __launch_bounds__(1024, 1) void rollout_chunk_kernel(QFwdParams p0, Q
     cx.ssa[le_d] = (uint16_t)(par ? ev.steps_alt : ev.steps)[de];
     cx.ssa[256 + le_d] = (uint16_t)(par ? ev.apples_alt : ev.apples)[de];
     for (int k = 0; k < N; ++k) cx.spq[le_d * N + k] = (uint16_t)pos16(pw[k]);
-#pragma unroll
-    for (int j = 0; j < kRollMaxR / 2; ++j)
-      if (2 * j < R) {
-        const uint4 g = gin[j];
-        rows[2 * j] = nib_pack4(g.x) | (nib_pack4(g.y) << 16);
-        if (2 * j + 1 < R) rows[2 * j + 1] = nib_pack4(g.z) | (nib_pack4(g.w) << 16);
-      }
+    roll_unpack_rows(gin, rows, R);
     cx.sdone[256 + le_d] = rc.done_prev[de];   // "previous step" slot of step 0 (parity 1)
     if (cx.writer) {   // every staging set the launch writes
       int ks = rc.set0;
@@ -2633,29 +2372,11 @@ __global__ __launch_bounds__(1024, 1) void rollout_chunk_kernel(QFwdParams p0, Q
   if (cx.writer && dvalid) {
     const bool dn = cx.sdone[lastp * 256 + le_d] != 0;
     int32_t* pout = (par ? ev.pos : ev.pos_alt) + (int64_t)de * N;
-    for (int k = 0; k < N; ++k) {
-      const uint32_t w = cx.spq[le_d * N + k];
-      pout[k] = dn ? ev.init_pos[k]
-                   : (int32_t)((((w >> 12) & 15) << 24) | (((w >> 8) & 15) << 16) | (((w >> 4) & 15) << 8) | (w & 15));
-    }
+    for (int k = 0; k < N; ++k) pout[k] = dn ? ev.init_pos[k] : pos32_from16(cx.spq[le_d * N + k]);
     (par ? ev.steps : ev.steps_alt)[de] = dn ? 0 : (int32_t)cx.ssa[le_d];
     (par ? ev.apples : ev.apples_alt)[de] = dn ? ev.init_apples : (int32_t)cx.ssa[256 + le_d];
-    uint4* gout = reinterpret_cast<uint4*>((par ? ev.grid : ev.grid_alt) + (int64_t)de * RC);
-    const uint4* ig = reinterpret_cast<const uint4*>(ev.init_grid);
-    const uint32_t* rows = cx.sgrid + le_d * roll_gbw(R);
-#pragma unroll
-    for (int j = 0; j < kRollMaxR / 2; ++j)
-      if (2 * j < R) {
-        uint4 v;
-        if (dn) {
-          v = ig[j];
-        } else {
-          const uint32_t a0 = rows[2 * j], a1 = 2 * j + 1 < R ? rows[2 * j + 1] : 0u;
-          v = make_uint4(nib_unpack4(a0 & 0xFFFFu), nib_unpack4(a0 >> 16), nib_unpack4(a1 & 0xFFFFu),
-                         nib_unpack4(a1 >> 16));
-        }
-        gout[j] = v;
-      }
+    roll_pack_rows(reinterpret_cast<uint4*>((par ? ev.grid : ev.grid_alt) + (int64_t)de * RC),
+                   cx.sgrid + le_d * roll_gbw(R), reinterpret_cast<const uint4*>(ev.init_grid), dn, R);
   }
   // ---- the last block to finish advances the launch state (every block has read it by then)
   __syncthreads();
@@ -2780,12 +2501,8 @@ __global__ __launch_bounds__(1024, 1) void agent_pre_h3_kernel(QFwdParams p0, QF
   const int bid = second ? (int)blockIdx.x - p0.nblocks : (int)blockIdx.x;
   const int agent = bid % p.N, tile = bid / p.N;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool exact = reinterpret_cast<const int*>(p.packed + 2 * p.g.agent_stride * p.N)[agent] != 0;
-  const float* src = p.packed + (exact ? 0 : (int64_t)p.N * p.g.agent_stride) + (int64_t)agent * p.g.agent_stride;
-  const int nchunk = (int)(p.g.agent_stride >> 8);
-  for (int c = wave; c < nchunk; c += 16)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                     (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
+  const bool exact = agent_range_guarded(p, agent);
+  image_dma(agent_image_src(p, agent, exact), wsm, (int)(p.g.agent_stride >> 8), 0, 16);
   __syncthreads();
   if (exact) {
     const int e32 = tile * 256 + wave * 32 + (lane & 31);
@@ -2811,11 +2528,7 @@ __global__ __launch_bounds__(1024, 1) void agent_pre_lds_kernel(QFwdParams p0, Q
   const int bid = second ? (int)blockIdx.x - p0.nblocks : (int)blockIdx.x;
   const int agent = bid % p.N, tile = bid / p.N;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* src = p.packed + (int64_t)agent * p.g.agent_stride;
-  const int nchunk = (int)(p.g.agent_stride >> 8);
-  for (int c = wave; c < nchunk; c += 16)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                     (__attribute__((address_space(3))) void*)(wsm + c * 256), 16, 0, 0);
+  image_dma(agent_image_src(p, agent, true), wsm, (int)(p.g.agent_stride >> 8), 0, 16);
   const int e = tile * 512 + wave * 32 + (lane & 31);
   const float* orow = obs_row_ptr(p, agent, e);
   __syncthreads();
@@ -3068,6 +2781,26 @@ static bool use_lds(const QFwdParams& p0, const QFwdParams* p1) {
   return bytes <= 160 * 1024 && p0.E >= 2048 && (!p1 || p1->E >= 2048);
 }
 
+// The supported (F1, G, H) shapes x AB = ceil(n_actions / 32) in {1, 2}: the one list every launch site dispatches
+// through. Calls f(F1, G, H, AB) with std::integral_constants (usable as template arguments in a generic lambda) and
+// stores its result in *rc; false (f not called) when the shape has no instantiation.
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <class F>
+static bool with_qnet_shape(const mm_qnet_dims* d, int* rc, F&& f) {
+  auto at = [&](auto F1, auto G, auto H) {
+    if (d->f1 != F1 || d->g != G || d->h != H) return false;
+    *rc = (d->n_actions + 31) / 32 == 1 ? f(F1, G, H, ic<1>{}) : f(F1, G, H, ic<2>{});
+    return true;
+  };
+  return at(ic<64>{}, ic<32>{}, ic<32>{}) || at(ic<64>{}, ic<64>{}, ic<64>{}) || at(ic<128>{}, ic<32>{}, ic<32>{}) ||
+         at(ic<64>{}, ic<32>{}, ic<64>{});
+}
+static bool qnet_shape_supported(const mm_qnet_dims* d) {
+  int rc;
+  return with_qnet_shape(d, &rc, [](auto, auto, auto, auto) { return 0; });
+}
+
 template <int F1, int G, int H, int AB>
 static int launch_fwd(QFwdParams p0, const QFwdParams* p1in, hipStream_t s) {
   QFwdParams p1 = p1in ? *p1in : p0;
@@ -3126,11 +2859,9 @@ static int make_params(const mm_qnet_dims* d, const float* packed, const mm_qfwd
 }
 
 static int dispatch(const mm_qnet_dims* d, const QFwdParams& p0, const QFwdParams* p1, hipStream_t s) {
-  const int AB = (d->n_actions + 31) / 32;
-  if (d->f1 == 64 && d->g == 32 && d->h == 32) return AB == 1 ? launch_fwd<64, 32, 32, 1>(p0, p1, s) : launch_fwd<64, 32, 32, 2>(p0, p1, s);
-  if (d->f1 == 64 && d->g == 64 && d->h == 64) return AB == 1 ? launch_fwd<64, 64, 64, 1>(p0, p1, s) : launch_fwd<64, 64, 64, 2>(p0, p1, s);
-  if (d->f1 == 128 && d->g == 32 && d->h == 32) return AB == 1 ? launch_fwd<128, 32, 32, 1>(p0, p1, s) : launch_fwd<128, 32, 32, 2>(p0, p1, s);
-  if (d->f1 == 64 && d->g == 32 && d->h == 64) return AB == 1 ? launch_fwd<64, 32, 64, 1>(p0, p1, s) : launch_fwd<64, 32, 64, 2>(p0, p1, s);
+  int rc;
+  if (with_qnet_shape(d, &rc, [&](auto F1, auto G, auto H, auto AB) { return launch_fwd<F1, G, H, AB>(p0, p1, s); }))
+    return rc;
   set_error("agent_q_fwd: unsupported (F1,G,H)=(%d,%d,%d)", d->f1, d->g, d->h);
   return MM_EINVAL;
 }
@@ -3188,18 +2919,11 @@ static int launch_pre_h3(QFwdParams p0, QFwdParams p1, hipStream_t s) {
 
 static int dispatch_split(const mm_qnet_dims* d, int phase, const QFwdParams& p0, const QFwdParams& p1,
                           hipStream_t s) {
-  const int AB = (d->n_actions + 31) / 32;
-#define MM_SPLIT(F1_, G_, H_)                                                                               \
-  if (d->f1 == F1_ && d->g == G_ && d->h == H_) {                                                           \
-    if (phase == 3)                                                                                         \
-      return AB == 1 ? launch_pre_h3<F1_, G_, H_, 1>(p0, p1, s) : launch_pre_h3<F1_, G_, H_, 2>(p0, p1, s); \
-    return AB == 1 ? launch_split<F1_, G_, H_, 1>(phase, p0, p1, s) : launch_split<F1_, G_, H_, 2>(phase, p0, p1, s); \
-  }
-  MM_SPLIT(64, 32, 32)
-  MM_SPLIT(64, 64, 64)
-  MM_SPLIT(128, 32, 32)
-  MM_SPLIT(64, 32, 64)
-#undef MM_SPLIT
+  int rc;
+  if (with_qnet_shape(d, &rc, [&](auto F1, auto G, auto H, auto AB) {
+        return phase == 3 ? launch_pre_h3<F1, G, H, AB>(p0, p1, s) : launch_split<F1, G, H, AB>(phase, p0, p1, s);
+      }))
+    return rc;
   set_error("agent_q_split: unsupported (F1,G,H)=(%d,%d,%d)", d->f1, d->g, d->h);
   return MM_EINVAL;
 }
@@ -3268,18 +2992,12 @@ int agent_q_rec_seq2(const mm_qnet_dims* d, const float* packed0, const mm_qfwd_
   QFwdParams p0, p1;
   RecSeq s0, s1;
   bool single;
-  const int rc = rec_seq_args(d, packed0, io0, e0, packed1, io1, e1, steps, reset, p0, p1, s0, s1, single);
+  int rc = rec_seq_args(d, packed0, io0, e0, packed1, io1, e1, steps, reset, p0, p1, s0, s1, single);
   if (rc) return rc;
-  const int AB = (d->n_actions + 31) / 32;
-#define MM_RSEQ(F1_, G_, H_)                                                                                    \
-  if (d->f1 == F1_ && d->g == G_ && d->h == H_)                                                                 \
-    return AB == 1 ? launch_rec_seq<F1_, G_, H_, 1>(p0, p1, s0, s1, single, s)                                  \
-                   : launch_rec_seq<F1_, G_, H_, 2>(p0, p1, s0, s1, single, s);
-  MM_RSEQ(64, 32, 32)
-  MM_RSEQ(64, 64, 64)
-  MM_RSEQ(128, 32, 32)
-  MM_RSEQ(64, 32, 64)
-#undef MM_RSEQ
+  if (with_qnet_shape(d, &rc, [&](auto F1, auto G, auto H, auto AB) {
+        return launch_rec_seq<F1, G, H, AB>(p0, p1, s0, s1, single, s);
+      }))
+    return rc;
   set_error("agent_q_rec_seq: unsupported (F1,G,H)=(%d,%d,%d)", d->f1, d->g, d->h);
   return MM_EINVAL;
 }
@@ -3345,9 +3063,7 @@ size_t rollout_step_lds(const mm_env* env, const mm_qnet_dims* d, int64_t n_envs
   // writer's grid stores)
   if (ev.N > kRollMaxN || ev.R > kRollMaxR || ev.C != 8 || (ev.R & 1)) return 0;
   if (n_envs < 2048 || n_envs != ev.E) return 0;
-  const bool known = (d->f1 == 64 && d->g == 32 && d->h == 32) || (d->f1 == 64 && d->g == 64 && d->h == 64) ||
-                     (d->f1 == 128 && d->g == 32 && d->h == 32) || (d->f1 == 64 && d->g == 32 && d->h == 64);
-  if (!known) return 0;
+  if (!qnet_shape_supported(d)) return 0;
   const size_t sm = roll_region(ev, g) + (size_t)roll_lds(ev.R, ev.C, ev.N).total;
   return sm <= 160 * 1024 ? sm : 0;
 }
@@ -3402,15 +3118,10 @@ int rollout_step(mm_env* env, const mm_qnet_dims* d, const float* packed_t, cons
   rs.err = reinterpret_cast<uint32_t*>(x->err);
   rs.begin = x->begin ? 1 : 0;
   rs.lds_env = (int)roll_region(env->d, p0.g);
-  const int AB = (d->n_actions + 31) / 32;
-#define MM_ROLL(F1_, G_, H_)                                                                             \
-  if (d->f1 == F1_ && d->g == G_ && d->h == H_)                                                          \
-    return AB == 1 ? launch_roll<F1_, G_, H_, 1>(p0, p1, rs, sm, s) : launch_roll<F1_, G_, H_, 2>(p0, p1, rs, sm, s);
-  MM_ROLL(64, 32, 32)
-  MM_ROLL(64, 64, 64)
-  MM_ROLL(128, 32, 32)
-  MM_ROLL(64, 32, 64)
-#undef MM_ROLL
+  if (with_qnet_shape(d, &rc, [&](auto F1, auto G, auto H, auto AB) {
+        return launch_roll<F1, G, H, AB>(p0, p1, rs, sm, s);
+      }))
+    return rc;
   set_error("rollout_step: unsupported (F1,G,H)");
   return MM_EINVAL;
 }
@@ -3507,16 +3218,10 @@ int rollout_chunk(mm_env* env, const mm_qnet_dims* d, const float* packed_t, con
   qnet_geometry(d, &g, &o);
   r.lds_env = (int)(((size_t)g.agent_stride * 4 + 15) & ~size_t(15));
   const int nb = 2 * tiles * d->n_agents;
-  const int AB = (d->n_actions + 31) / 32;
-#define MM_ROLLC(F1_, G_, H_)                                                                       \
-  if (d->f1 == F1_ && d->g == G_ && d->h == H_)                                                     \
-    return AB == 1 ? launch_chunk<F1_, G_, H_, 1>(p0, p1, r, nb, sm, s)                             \
-                   : launch_chunk<F1_, G_, H_, 2>(p0, p1, r, nb, sm, s);
-  MM_ROLLC(64, 32, 32)
-  MM_ROLLC(64, 64, 64)
-  MM_ROLLC(128, 32, 32)
-  MM_ROLLC(64, 32, 64)
-#undef MM_ROLLC
+  if (with_qnet_shape(d, &rc, [&](auto F1, auto G, auto H, auto AB) {
+        return launch_chunk<F1, G, H, AB>(p0, p1, r, nb, sm, s);
+      }))
+    return rc;
   set_error("rollout_chunk: unsupported (F1,G,H)");
   return MM_EINVAL;
 }

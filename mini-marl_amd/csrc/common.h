@@ -80,11 +80,8 @@ __device__ __forceinline__ uint32_t rng_mod_small_u(uint64_t r, uint32_t m, uint
 }
 // max(x, 0) on the bit pattern: one v_max_i32 (negative floats are negative integers; no canonicalising v_max_f32
 // pair), equal to fmaxf(x, 0) for every non-NaN x but -0 -> +0
-#ifndef MM_RELU_BITS
-#define MM_RELU_BITS 1
-#endif
 __device__ __forceinline__ float relu_bits(float x) {
-  return MM_RELU_BITS ? __int_as_float(max(__float_as_int(x), 0)) : fmaxf(x, 0.0f);
+  return __int_as_float(max(__float_as_int(x), 0));
 }
 
 // Debug timing traces: a static device buffer of 4096 u64 slots, allocated when the named
