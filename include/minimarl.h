@@ -733,6 +733,31 @@ int mm_offq_q_values(const mm_offq_dims* d, const float* P, const float* obs, co
                      int32_t L, int64_t R, void* ws, int64_t ws_bytes, mm_stream_t s);
 /* soft_update: target <- target * (1 - tau) + source * tau over n floats (tau = 1: hard update). */
 int mm_offq_soft_update(float* target, const float* source, int64_t n, double tau, mm_stream_t s);
+/* Episode collector (RecRunner.collect_rollout, offpolicy/runner/shared/magym_runner.py:40-141, for E lockstep
+ * Checkers envs): ONE launch runs a whole T-step episode of every env from reset with the behavior agent net P
+ * (hidden zero at t = 0, carried over all T steps, not reset at done) and per-(env, agent) epsilon-greedy:
+ * ctr = counter + t, u = rng_uniform(rng_draw(seed, ctr, e, n)), random action rng_draw(seed ^ 0x5bd1e995, ctr, e,
+ * n) % A, explore iff u < *eps, greedy = first maximum. A finished env is not stepped again: rewards 0, the
+ * observation stays the terminal one, dones stay 1. Outputs in mm_erb_insert's layout: obs [T+1, E, N, D] (index T
+ * = the final observation), acts one-hot [T, E, N, A], rewards / dones [T, E, N, 1], dones_env [T, E, 1];
+ * share_obs is not written (it is obs viewed as [T+1, E, N*D]: mm_erb_insert_concat). common_reward: every agent
+ * gets the f32 sum of the step's rewards in agent order (base_runner.py:346-348). q_out [T, E, N, A] (all Q values)
+ * and ret_out [E] (sum over t of agent 0's stored reward) may be NULL. eps: device f32 [1]; counter: device u64 [1]
+ * read at entry, or NULL to use counter0. P and the outputs must be 16-byte aligned. The env handle supplies the
+ * rules and the reset state only: its live state is neither read nor written, so any handle with the same
+ * configuration gives the same episodes whatever was stepped on it before. Supported (mm_offq_collect_supported
+ * returns 1): local observation D = 47, H = 64, A = 5, dims.n_agents = the env's agents <= 10, 8 columns. */
+typedef struct mm_offq_collect_io {
+  const float* eps;
+  const uint64_t* counter;
+  uint64_t counter0, seed;
+  int32_t common_reward;
+  float* obs; float* acts; float* rewards; float* dones; float* dones_env;
+  float* q_out; float* ret_out;
+} mm_offq_collect_io;
+int mm_offq_collect_supported(const mm_env* env, const mm_offq_dims* d, int64_t n_envs, int32_t T);
+int mm_offq_collect(mm_env* env, const mm_offq_dims* d, const float* P, const mm_offq_collect_io* io, int64_t n_envs,
+                    int32_t T, mm_stream_t s);
 
 /* ------------------------------------------------------- ma_gym Switch corridor env (mm_switch_*) */
 /* gym.make("ma_gym:Switch2-v0", max_steps, step_cost) (qmix/_config.py:14-19, qmix/main.py:66-71,
@@ -803,6 +828,10 @@ void mm_erb_destroy(mm_erb* b);
 /* RecPolicyBuffer.insert + the prioritized leaf writes (rec_buffer.py:146-190, 262-270); n <= size.
  * idx_range_host (may be NULL): int64 [n], the ring slots written (host memory, filled at once). */
 int mm_erb_insert(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s);
+/* mm_erb_insert without a materialised share_obs: src->share_obs is ignored and every stored share_obs row is the
+ * concatenation of the agents' observations, read from src->obs (requires S == N * D; stored once per step with
+ * same_share, once per agent otherwise). Everything else is mm_erb_insert. */
+int mm_erb_insert_concat(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s);
 int64_t mm_erb_len(const mm_erb* b);          /* filled_i */
 int64_t mm_erb_current(const mm_erb* b);      /* current_i */
 int64_t mm_erb_it_capacity(const mm_erb* b);

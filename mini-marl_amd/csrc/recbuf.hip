@@ -42,6 +42,7 @@ struct ErbField {
   uint32_t L, R;       // steps, floats per (slot, step) in the store
   uint32_t R_in;       // insert: floats per (step, episode) in the source (>= R: share keeps agent 0)
   uint32_t Nf;         // gather: agent split of a row (row = Nf x X) -> [Nf, L, B, X]
+  uint32_t Rw;         // insert_concat: the source row repeats after Rw floats (0: it does not)
 };
 struct ErbFieldSet {
   ErbField f[6];
@@ -49,13 +50,16 @@ struct ErbFieldSet {
 };
 
 // insert: store[(slot(e) L + l) R + r] = src[(l n + e) R_in + r], slot(e) = (current + e) % size
+// (WRAP, insert_concat: r % Rw on the source side where the field has Rw != 0)
+template <bool WRAP>
 __global__ __launch_bounds__(256) void erb_insert_kernel(ErbFieldSet fs, uint32_t n, int64_t current, int64_t size) {
   const ErbField& F = fs.f[blockIdx.y];
   const uint64_t total = (uint64_t)F.L * n * F.R;
   for (uint64_t o = (uint64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (uint64_t)gridDim.x * 256) {
     const uint64_t r = o % F.R, le = o / F.R, e = le % n, l = le / n;
     const int64_t slot = (current + e) % size;
-    F.store[((size_t)slot * F.L + l) * F.R + r] = F.src[((size_t)l * n + e) * F.R_in + r];
+    const uint64_t rs = (WRAP && F.Rw) ? r % F.Rw : r;
+    F.store[((size_t)slot * F.L + l) * F.R + r] = F.src[((size_t)l * n + e) * F.R_in + rs];
   }
 }
 
@@ -280,19 +284,34 @@ void mm_erb_destroy(mm_erb* b) {
   delete b;
 }
 
-int mm_erb_insert(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s) {
-  MM_REQUIRE(b && src && n >= 1 && n <= b->size, "erb_insert: bad arguments (n must be in [1, buffer_size])");
-  const float* in[kFieldRows] = {src->obs, src->share_obs, src->acts, src->rewards, src->dones, src->dones_env};
+// mm_erb_insert / mm_erb_insert_concat (concat: share_obs rows are built from the obs field)
+static int erb_insert_impl(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s,
+                           bool concat) {
+  const char* who = concat ? "erb_insert_concat" : "erb_insert";
+  MM_REQUIRE(b && src && n >= 1 && n <= b->size, "%s: bad arguments (n must be in [1, buffer_size])", who);
+  MM_REQUIRE(!concat || b->d.S == b->d.N * b->d.D, "erb_insert_concat: share_obs dim S (%d) must be N * D (%d)",
+             b->d.S, b->d.N * b->d.D);
+  const float* in[kFieldRows] = {src->obs, concat ? src->obs : src->share_obs, src->acts, src->rewards, src->dones,
+                                 src->dones_env};
   mm::ErbFieldSet fs;
   fs.nf = kFieldRows;
   for (int i = 0; i < kFieldRows; ++i) {
-    MM_REQUIRE(in[i] != nullptr, "erb_insert: field %d is NULL", i);
-    fs.f[i] = {b->f[i], in[i], nullptr, (uint32_t)b->L[i], (uint32_t)b->R[i], (uint32_t)b->R[i], 1u};
+    MM_REQUIRE(in[i] != nullptr, "%s: field %d is NULL", who, i);
+    fs.f[i] = {b->f[i], in[i], nullptr, (uint32_t)b->L[i], (uint32_t)b->R[i], (uint32_t)b->R[i], 1u, 0u};
   }
-  if (b->d.same_share) fs.f[1].R_in = (uint32_t)(b->d.N * b->d.S);   // [T+1, n, N, S] -> agent 0
+  if (concat) {
+    fs.f[1].R_in = (uint32_t)b->d.S;   // a source row = the step's [N, D] observations = one share_obs row
+    fs.f[1].Rw = (uint32_t)b->d.S;     // (stored per agent without same_share: the row repeats)
+  } else if (b->d.same_share) {
+    fs.f[1].R_in = (uint32_t)(b->d.N * b->d.S);   // [T+1, n, N, S] -> agent 0
+  }
   hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(mm::erb_insert_kernel, dim3(erb_grid(fs, n), kFieldRows), dim3(256), 0, st, fs, (uint32_t)n,
-                     b->current, b->size);
+  if (concat)
+    hipLaunchKernelGGL(mm::erb_insert_kernel<true>, dim3(erb_grid(fs, n), kFieldRows), dim3(256), 0, st, fs,
+                       (uint32_t)n, b->current, b->size);
+  else
+    hipLaunchKernelGGL(mm::erb_insert_kernel<false>, dim3(erb_grid(fs, n), kFieldRows), dim3(256), 0, st, fs,
+                       (uint32_t)n, b->current, b->size);
   MM_HIP_CHECK(hipGetLastError());
   const int64_t first = b->current;
   if (b->d.prioritized) {
@@ -308,6 +327,14 @@ int mm_erb_insert(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_r
   b->current = (first + n - 1) % b->size + 1;
   b->filled = std::min<int64_t>(b->filled + n, b->size);
   return MM_OK;
+}
+
+int mm_erb_insert(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s) {
+  return erb_insert_impl(b, n, src, idx_range_host, s, false);
+}
+
+int mm_erb_insert_concat(mm_erb* b, int32_t n, const mm_erb_fields* src, int64_t* idx_range_host, mm_stream_t s) {
+  return erb_insert_impl(b, n, src, idx_range_host, s, true);
 }
 
 int64_t mm_erb_len(const mm_erb* b) { return b ? b->filled : -1; }

@@ -6,4 +6,12 @@ GPU; the first op loads the library and raises if it was not built.
 """
 from ._lib import lib, symbols  # noqa: F401
 
-__all__ = ["lib", "symbols"]
+__all__ = ["lib", "symbols", "OffQCollector", "OffQRunner"]
+
+
+def __getattr__(name):
+    # the offpolicy episode collector and runner (minimarl.offq_runner), imported on first use
+    if name in ("OffQCollector", "OffQRunner"):
+        from . import offq_runner
+        return getattr(offq_runner, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

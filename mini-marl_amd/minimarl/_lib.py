@@ -375,6 +375,19 @@ _SIGS += [
 ]
 
 
+class OffqCollectIO(ctypes.Structure):
+    """mm_offq_collect_io (include/minimarl.h)"""
+    _fields_ = [("eps", c_vp), ("counter", c_vp), ("counter0", c_u64), ("seed", c_u64), ("common_reward", c_i32),
+                ("obs", c_vp), ("acts", c_vp), ("rewards", c_vp), ("dones", c_vp), ("dones_env", c_vp),
+                ("q_out", c_vp), ("ret_out", c_vp)]
+
+
+_SIGS += [
+    ("mm_offq_collect_supported", c_i32, [c_vp, _OD, c_i64, c_i32]),
+    ("mm_offq_collect", c_i32, [c_vp, _OD, c_vp, ctypes.POINTER(OffqCollectIO), c_i64, c_i32, c_vp]),
+]
+
+
 # ------------------------------------------------------------------ offpolicy episode replay (mm_erb_*)
 class ErbDims(ctypes.Structure):
     _fields_ = [("T", c_i32), ("N", c_i32), ("D", c_i32), ("S", c_i32), ("A", c_i32), ("same_share", c_i32),
@@ -391,6 +404,7 @@ _SIGS += [
     ("mm_erb_create", c_i32, [_ED, c_i64, c_f64, ctypes.POINTER(c_vp)]),
     ("mm_erb_destroy", None, [c_vp]),
     ("mm_erb_insert", c_i32, [c_vp, c_i32, ctypes.POINTER(ErbFields), c_vp, c_vp]),
+    ("mm_erb_insert_concat", c_i32, [c_vp, c_i32, ctypes.POINTER(ErbFields), c_vp, c_vp]),
     ("mm_erb_len", c_i64, [c_vp]),
     ("mm_erb_current", c_i64, [c_vp]),
     ("mm_erb_it_capacity", c_i64, [c_vp]),

@@ -111,6 +111,47 @@ class MappoTrainConfig:
 
 
 @dataclass
+class OffQTrainConfig:
+    """offpolicy/config.py defaults of the episode-level QMix / VDN runner (minimarl.offq_runner.OffQRunner).
+    ``n_envs`` is lockstep-specific: the episodes collected per iteration (the reference's ``num_envs``, fixed at 1
+    there, base_runner.py:51)."""
+    algorithm_name: str = "qmix"        # "qmix" | "vdn"
+    n_envs: int = 32
+    n_agents: int = 2
+    step_cost: float = -0.01
+    episode_length: int = 100           # also the env's max_steps
+    buffer_size: int = 10000
+    batch_size: int = 32
+    hidden_size: int = 64
+    mixer_hidden_dim: int = 32
+    hypernet_hidden_dim: int = 64
+    lr: float = 5e-4
+    opti_eps: float = 1e-5
+    gamma: float = 0.99
+    max_grad_norm: float = 10.0
+    use_double_q: bool = True
+    use_huber_loss: bool = False
+    huber_delta: float = 10.0
+    use_per: bool = True
+    per_nu: float = 0.9
+    per_alpha: float = 0.6
+    per_eps: float = 1e-6
+    per_beta_start: float = 0.4
+    use_same_share_obs: bool = True
+    use_common_reward: bool = True
+    use_soft_update: bool = True
+    tau: float = 0.005
+    hard_update_interval_episode: int = 200
+    epsilon_start: float = 1.0
+    epsilon_finish: float = 0.05
+    epsilon_anneal_time: int = 50000
+    num_random_episodes: int = 5
+    train_interval_episode: int = 1
+    num_env_steps: int = 2000000
+    seed: int = 1
+
+
+@dataclass
 class Preset:
     name: str
     description: str

@@ -127,6 +127,28 @@ class RecReplayBuffer:
         self._keep = keep           # alive until the copies ran (stream-ordered reuse is safe after)
         return idx
 
+    def insert_collected(self, num_insert_episodes, fields, p_id="policy_0"):
+        """``insert`` for the device collector's episodes (minimarl.offq_runner.OffQCollector): ``fields`` holds
+        the device tensors obs [T+1, n, N, D], acts, rewards, dones, dones_env in the insert layout and no
+        share_obs; each stored share_obs row is the step's observations concatenated over agents
+        (mm_erb_insert_concat, S == N * D). Returns the ring slots written (np.ndarray)."""
+        n = int(num_insert_episodes)
+        pb = self.policy_buffers[p_id]
+        T = self.episode_length
+        src = {}
+        for k, shp in (("obs", (T + 1, n, pb.N, pb.D)), ("acts", (T, n, pb.N, pb.A)), ("rewards", (T, n, pb.N, 1)),
+                       ("dones", (T, n, pb.N, 1)), ("dones_env", (T, n, 1))):
+            t = fields[k]
+            assert torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), k
+            assert tuple(t.shape) == shp, ("different dimension!", k, tuple(t.shape), shp)
+            src[k] = t
+        idx = np.zeros(n, np.int64)
+        f = ErbFields(ptr(src["obs"]), None, ptr(src["acts"]), ptr(src["rewards"]), ptr(src["dones"]),
+                      ptr(src["dones_env"]))
+        check(lib().mm_erb_insert_concat(pb._h, n, ctypes.byref(f), idx.ctypes.data_as(ctypes.c_void_p),
+                                         stream_handle(self.device)), "erb_insert_concat")
+        return idx
+
     def _next_counter(self):
         self._draws += 1
         return self._draws - 1
