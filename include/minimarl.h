@@ -702,8 +702,12 @@ int mm_mappo_insert(const uint8_t* done, int32_t n_agents, int32_t hidden, int64
  * Batch = PrioritizedRecReplayBuffer.sample layout (rec_buffer.py:192-240): obs [N, T+1, B, D],
  * share_obs [T+1, B, S], acts one-hot [N, T, B, A], rewards [N, T, B] (agent 0's are used,
  * qmix.py:169), dones_env [T, B], is_weight [B] (NULL: no PER). Supported: H = 64, A = 5,
- * D in {47, 94}; QMIX: hypernet_layers = 2, any S, N*K <= 4096. */
+ * D in {47, 94}; QMIX: hypernet_layers = 2, any S, mixer_hidden K <= MM_OFFQ_MAX_MIXER_HIDDEN (the
+ * mixer kernels give one lane of a 64-lane wave to each mixing unit), N*K <= 4096. For a larger K
+ * mm_offq_param_counts, mm_offq_mixer_offsets and mm_offq_loss_grad return MM_EINVAL and
+ * mm_offq_workspace_bytes returns -1. */
 enum { MM_OFFQ_VDN = 0, MM_OFFQ_QMIX = 1 };
+#define MM_OFFQ_MAX_MIXER_HIDDEN 64
 typedef struct mm_offq_dims {
   int32_t n_agents, obs_dim, hidden, n_actions;
   int32_t mixer;                                   /* MM_OFFQ_VDN / MM_OFFQ_QMIX */

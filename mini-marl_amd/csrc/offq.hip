@@ -1466,6 +1466,10 @@ static int check_dims(const mm_offq_dims* d) {
                  (d->state_dim >= 1 && d->mixer_hidden >= 1 && d->hyper_hidden >= 1 &&
                   (int64_t)d->n_agents * d->mixer_hidden <= 4096),
              "offq: QMIX needs state_dim, mixer_hidden, hyper_hidden >= 1 and N*K <= 4096");
+  // the mixer kernels give one lane of a 64-lane wave to each mixing unit (lanes_sum, mix_rows_per_block)
+  MM_REQUIRE(d->mixer == MM_OFFQ_VDN || d->mixer_hidden <= MM_OFFQ_MAX_MIXER_HIDDEN,
+             "offq: mixer_hidden %d is above the limit of %d (one wave lane per mixing unit)", d->mixer_hidden,
+             MM_OFFQ_MAX_MIXER_HIDDEN);
   return MM_OK;
 }
 

@@ -37,6 +37,7 @@ MIXER_KEYS = ["hyper_w1.0.weight", "hyper_w1.0.bias", "hyper_w1.2.weight", "hype
               "hyper_w2.0.weight", "hyper_w2.0.bias", "hyper_w2.2.weight", "hyper_w2.2.bias",
               "hyper_b1.weight", "hyper_b1.bias",
               "hyper_b2.0.weight", "hyper_b2.0.bias", "hyper_b2.2.weight", "hyper_b2.2.bias"]
+MAX_MIXER_HIDDEN = 64     # MM_OFFQ_MAX_MIXER_HIDDEN (include/minimarl.h)
 
 
 class OffQMix:
@@ -47,6 +48,9 @@ class OffQMix:
                  use_double_q=True, use_per=True, use_huber_loss=False, huber_delta=10.0, per_nu=0.9,
                  per_eps=1e-6, tau=0.005, device="cuda", seed=None, grad_allreduce=None):
         assert mixer in ("qmix", "vdn")
+        if mixer == "qmix" and int(mixer_hidden) > MAX_MIXER_HIDDEN:
+            raise ValueError(f"OffQMix: mixer_hidden {int(mixer_hidden)} is above the limit of {MAX_MIXER_HIDDEN} "
+                             "(the mixer kernels give one wave lane to each mixing unit)")
         self.N, self.D, self.A, self.H = int(n_agents), int(obs_dim), int(n_actions), int(hidden)
         self.T, self.B = int(episode_length), int(batch_size)
         self.mixer_kind = mixer

@@ -1,5 +1,7 @@
 """Oracle (test infrastructure only): the episode-level recurrent QMix / VDN trainer of the
-reference's ``offpolicy/`` fork restated in torch-CPU fp32 (autograd for the gradients only).
+reference's ``offpolicy/`` fork restated in torch-CPU fp32 (autograd for the gradients only);
+``dtype=torch.float64`` runs the same step in double precision (the reference of
+tests/test_gpu_offq_shapes.py).
 
 Pinned against tests/golden/offq_*.npz (tests/golden/make_golden_offq.py runs the reference).
 
@@ -53,11 +55,13 @@ def mixer_from_state(sd, prefix="m."):
     return {k: torch.tensor(np.asarray(sd[prefix + k]), dtype=torch.float32) for k in MIXER_KEYS}
 
 
-def agent_q_seq(P, x, h0=None):
-    """x [L, R, D] -> q [L, R, A], final hidden [R, H]."""
+def agent_q_seq(P, x, h0=None, dtype=torch.float32):
+    """x [L, R, D] -> q [L, R, A], final hidden [R, H]; everything in ``dtype``."""
     L, R, _ = x.shape
     H = P["Whh"].shape[1]
-    h = torch.zeros(R, H) if h0 is None else h0
+    P = {k: v.to(dtype) for k, v in P.items()}
+    x = x.to(dtype)
+    h = torch.zeros(R, H, dtype=dtype) if h0 is None else h0.to(dtype)
     f = layer_norm(x, P["ln0_w"], P["ln0_b"])
     f = layer_norm(torch.relu(f @ P["W1"].t() + P["b1"]), P["ln1_w"], P["ln1_b"])
     f = layer_norm(torch.relu(f @ P["W2"].t() + P["b2"]), P["ln2_w"], P["ln2_b"])
@@ -91,24 +95,33 @@ def stack_agents(x):
 
 
 def train_batch(P, M, PT, MT, batch, mixer="qmix", double_q=True, use_per=True, huber=False, gamma=0.99,
-                huber_delta=10.0, per_nu=0.9, per_eps=1e-6, K=32, max_norm=10.0, lr=5e-4, eps=1e-5, adam_state=None):
+                huber_delta=10.0, per_nu=0.9, per_eps=1e-6, K=32, max_norm=10.0, lr=5e-4, eps=1e-5, adam_state=None,
+                dtype=torch.float32, update=True):
     """One QMix.train_policy_on_batch. batch: dict of arrays (reference sample layout).
-    Returns (new P, new M, info dict with grads / loss / priorities)."""
-    obs = torch.tensor(batch["obs"])                   # [N, T+1, B, D]
+    Returns (new P, new M, info dict with grads / loss / priorities). ``dtype``: the whole step
+    (forward, autograd, clip, Adam, priorities) runs in it; torch.float64 makes the oracle the
+    high-precision reference of the GPU tests. ``update=False`` stops after the TD errors
+    (info = {"err", "mask"} only; P and M come back unchanged)."""
+    def arr(x):
+        return torch.tensor(x).to(dtype)
+
+    P, PT = ({k: v.to(dtype) for k, v in d.items()} for d in (P, PT))
+    M, MT = ({k: v.to(dtype) for k, v in d.items()} for d in (M, MT))
+    obs = arr(batch["obs"])                            # [N, T+1, B, D]
     N, T1, B, _ = obs.shape
     T = T1 - 1
     xs = stack_agents(obs)                             # [T+1, N*B, D]
-    acts = stack_agents(torch.tensor(batch["acts"]))   # [T, N*B, A]
-    share = torch.tensor(batch["share_obs"])           # [T+1, B, S]
-    rew = torch.tensor(batch["rewards"])[0, :, :, 0]   # [T, B] (agent 0's reward)
-    dn = torch.tensor(batch["dones_env"])[:, :, 0]     # [T, B]
+    acts = stack_agents(arr(batch["acts"]))            # [T, N*B, A]
+    share = arr(batch["share_obs"])                    # [T+1, B, S]
+    rew = arr(batch["rewards"])[0, :, :, 0]            # [T, B] (agent 0's reward)
+    dn = arr(batch["dones_env"])[:, :, 0]              # [T, B]
     p = {k: v.detach().clone().requires_grad_(True) for k, v in P.items()}
     m = {k: v.detach().clone().requires_grad_(True) for k, v in M.items()} if mixer == "qmix" else {}
-    q_all, _ = agent_q_seq(p, xs)                      # [T+1, NB, A]
+    q_all, _ = agent_q_seq(p, xs, dtype=dtype)         # [T+1, NB, A]
     a_idx = acts.max(-1)[1]
     q_taken = q_all[:-1].gather(2, a_idx.unsqueeze(-1))[..., 0]   # [T, NB]
     with torch.no_grad():
-        qt_all, _ = agent_q_seq(PT, xs)
+        qt_all, _ = agent_q_seq(PT, xs, dtype=dtype)
         if double_q:
             g = q_all.max(-1)[1]
             nq = qt_all.gather(2, g.unsqueeze(-1))[..., 0]
@@ -123,18 +136,20 @@ def train_batch(P, M, PT, MT, batch, mixer="qmix", double_q=True, use_per=True, 
             nqtot = qmixer(MT, nqa, share[1:], K)
     else:
         qtot, nqtot = qa.sum(-1), nqa.sum(-1)
-    bad = torch.cat([torch.zeros(1, B), dn[:T - 1]], 0)
+    bad = torch.cat([torch.zeros(1, B, dtype=dtype), dn[:T - 1]], 0)
     y = rew + (1 - dn) * gamma * nqtot
     err = (qtot - y.detach()) * (1 - bad)
+    if not update:
+        return P, M, {"err": err.detach(), "mask": 1 - bad}
     if huber:
         ae = err.abs()
         le = torch.where(ae <= huber_delta, err ** 2 / 2, huber_delta * (ae - huber_delta / 2))
     else:
         le = err ** 2
     if use_per:
-        w = torch.tensor(batch["is_weight"])
+        w = arr(batch["is_weight"])
         loss = (le.sum(0) * w).sum() / (1 - bad).sum()
-        td = err.abs().detach().numpy().astype(np.float32)
+        td = err.abs().detach().numpy()
         prio = ((1 - per_nu) * td.mean(0) + per_nu * td.max(0)) + per_eps
     else:
         loss = le.sum() / (1 - bad).sum()
@@ -150,7 +165,7 @@ def train_batch(P, M, PT, MT, batch, mixer="qmix", double_q=True, use_per=True, 
     P2 = {k: new[k] for k in P}
     M2 = {k: new["m:" + k] for k in M} if mixer == "qmix" else M
     info = {"loss": float(loss.detach()), "grad_norm": float(total), "q_tot": float((qtot.detach() * (1 - bad)).mean()),
-            "grads": G, "priorities": prio, "err": err.detach()}
+            "grads": G, "raw_grads": dict(zip(keys, grads)), "priorities": prio, "err": err.detach(), "mask": 1 - bad}
     return P2, M2, info
 
 
