@@ -133,9 +133,10 @@ class RecBufferOracle:
         if self.prioritized:
             leaves = np.arange(len(rng)) if self.leaf_mode == "reference" else rng
             val = self.max_p ** self.alpha       # Python float, or np.float32 once a priority exceeded 1
-            for i in leaves:                     # one __setitem__ per leaf, as the reference loops
-                self.sum.set(i, val)
-                self.min.set(i, val)
+            # the reference loops one __setitem__ per leaf; one call for all of them leaves the same trees (the
+            # leaves are distinct and every ancestor is op(left, right) of its final children) in 1 / n of the work
+            self.sum.set(leaves, val)
+            self.min.set(leaves, val)
         return rng
 
     def sample_inds(self, inds):
