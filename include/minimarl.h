@@ -663,6 +663,19 @@ int mm_mappo_bwd(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, mm_stream_t
 int64_t mm_mappo_grad_scratch_count(const mm_mappo_dims* d, int32_t L, int32_t T, int64_t en);
 int mm_mappo_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const float* h_actor, const float* h_critic,
                   float* grad_actor, float* grad_critic, float* scratch, mm_stream_t s);
+/* mm_mappo_grad over one PPO minibatch (recurrent_generator's sampler, shared_buffer.py:318-331): the n_chunks
+ * L-step chunks listed in chunks, a device int32[n_chunks] in the buffer's NATIVE chunk numbering c = kc * en + e
+ * (kc in [0, T / L): the chunk covers steps kc L .. kc L + L - 1 of row e; the reference numbers the same chunk
+ * e * (T / L) + kc). Entries must be distinct and in [0, (T / L) * en); they are not checked on the device. The
+ * recurrent pass handles chunk chunks[32 t + ci] in lane ci of tile t; the MLP pass runs over the list's
+ * n_chunks * L row-steps (the list cut into blocks of en chunks, each block step-major like the buffer, so that the
+ * list 0 .. (T / L) * en - 1 reproduces mm_mappo_grad bit for bit) and reads only the d loss / d x2 rows this call's
+ * recurrent pass wrote. Loss seeds divide
+ * by stats[MM_MST_ACTIVE_SUM] (the minibatch's, see mm_mappo_mb_stats); advantages keep the whole buffer's
+ * ADV_MEAN / ADV_STD. Same scratch as mm_mappo_grad. Needs L | T, 1 <= n_chunks <= (T / L) * en < 2^31. */
+int mm_mappo_grad_mb(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const int32_t* chunks, int64_t n_chunks,
+                     const float* h_actor, const float* h_critic, float* grad_actor, float* grad_critic,
+                     float* scratch, mm_stream_t s);
 /* R_MAPPOPolicy.evaluate_actions (rmappo_policy.py:101-136; RNNLayer's masked segments, rnn.py:24-80; the
  * Categorical head, distributions.py:55-68): a TRAIN-mode forward of both nets (a: T = L steps of EN chunks, rows
  * t*EN + en, chunk-start hiddens at h_in slot 0, masks [T, EN], save buffers), then per row the value, the log-prob
@@ -684,6 +697,12 @@ int mm_mappo_gae(const float* rew, const float* value_preds, const float* masks,
 int mm_mappo_adv_stats(const float* returns, const float* value_preds, const float* active, const float* vn,
                        float* adv, int64_t rows, double* partial, float* stats, mm_stream_t s);
 int mm_mappo_stats_from_sums(const double* sums, int64_t rows, float* stats, mm_stream_t s);
+/* The moments of one minibatch (chunks: as in mm_mappo_grad_mb) over its n_chunks * L row-steps: writes
+ * stats[MM_MST_ACTIVE_SUM] (count of active rows), [RET_MEAN] and [RET_SQ_MEAN] (f64 sums, fixed order) and leaves
+ * the other slots (ADV_MEAN / ADV_STD of the whole buffer, VN_MEAN / VN_STD) alone. partial: device double[3 * 256].
+ * Followed by mm_mappo_vn_update it is the minibatch's ValueNorm.update(return_batch) (ramppo_network.py:72-73). */
+int mm_mappo_mb_stats(const float* returns, const float* active, const int32_t* chunks, int64_t n_chunks, int32_t L,
+                      int32_t T, int64_t en, double* partial, float* stats, mm_stream_t s);
 /* One ValueNorm.update with the batch moments in stats, then stats[VN_MEAN/VN_STD]. */
 int mm_mappo_vn_update(float* vn, float* stats, double beta, mm_stream_t s);
 /* After env.step: masks/active of slot t+1, zero hiddens of done envs (done [E] u8); increments

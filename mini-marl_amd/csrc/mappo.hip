@@ -15,6 +15,8 @@
 // broadcast (the net's whole parameter vector, ~38 KB, is staged per block). The canonical
 // flat parameter layout (MGeo) is 16-byte aligned with W1 rows padded to Dp, so it IS the LDS
 // image (no pack step) and the Adam state shares it (pads stay exactly zero).
+#include <algorithm>
+
 #include "common.h"
 #include "minimarl.h"
 #include "trunk.h"
@@ -602,6 +604,62 @@ __global__ void mappo_stats_from_sums_kernel(const double* sums, int64_t R, floa
   stats[MM_MST_RET_SQ_MEAN] = (float)(sr2 / (double)R);
 }
 
+// Minibatch moments over the n_chunks * L row-steps of a chunk list (native numbering kc * EN + en; step l of the
+// chunk = buffer row (kc L + l) EN + en; one chunk per thread): block partials [3] of (active count, sum ret,
+// sum ret^2), f64, summed in a fixed order by mappo_mb_stats_kernel.
+__global__ __launch_bounds__(256) void mappo_mb_moments_kernel(const float* __restrict__ ret,
+                                                               const float* __restrict__ active,
+                                                               const int32_t* __restrict__ chunks, int64_t n_chunks,
+                                                               int L, int64_t EN, double* __restrict__ part) {
+  __shared__ double sh[3][256];
+  double n = 0, sr = 0, sr2 = 0;
+  for (int64_t j = blockIdx.x * 256ll + threadIdx.x; j < n_chunks; j += (int64_t)gridDim.x * 256) {
+    const uint32_t c = (uint32_t)chunks[j], kc = c / (uint32_t)EN, en = c - kc * (uint32_t)EN;   // (c < 2^31)
+    for (int l = 0; l < L; ++l) {
+      const int64_t row = ((int64_t)kc * L + l) * EN + en;
+      if (active[row] != 0.0f) n += 1.0;
+      sr += ret[row];
+      sr2 += (double)ret[row] * ret[row];
+    }
+  }
+  sh[0][threadIdx.x] = n;
+  sh[1][threadIdx.x] = sr;
+  sh[2][threadIdx.x] = sr2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w)
+      for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) part[blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// the minibatch's loss denominator and ValueNorm batch moments; the advantage and ValueNorm slots stay
+// (one wave: lane t sums the partials t, t + 64, ..., lane 0 the 64 lane sums in lane order -- a fixed order)
+__global__ __launch_bounds__(64) void mappo_mb_stats_kernel(const double* part, int nb, int64_t R, float* stats) {
+  __shared__ double sh[3][64];
+  double n = 0, sr = 0, sr2 = 0;
+  for (int b = threadIdx.x; b < nb; b += 64) {
+    n += part[b * 3];
+    sr += part[b * 3 + 1];
+    sr2 += part[b * 3 + 2];
+  }
+  sh[0][threadIdx.x] = n;
+  sh[1][threadIdx.x] = sr;
+  sh[2][threadIdx.x] = sr2;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  n = sr = sr2 = 0;
+  for (int t = 0; t < 64; ++t) {
+    n += sh[0][t];
+    sr += sh[1][t];
+    sr2 += sh[2][t];
+  }
+  stats[MM_MST_ACTIVE_SUM] = (float)n;
+  stats[MM_MST_RET_MEAN] = (float)(sr / (double)R);
+  stats[MM_MST_RET_SQ_MEAN] = (float)(sr2 / (double)R);
+}
+
 // One ValueNorm.update(returns) (valuenorm.py:37-54, f32, weight = beta) followed by the
 // normalisation constants for this epoch's value loss.
 __global__ void mappo_vn_update_kernel(float* vn, float* stats, float w, float omw) {
@@ -892,6 +950,22 @@ int mm_mappo_adv_stats(const float* returns, const float* value_preds, const flo
 int mm_mappo_stats_from_sums(const double* sums, int64_t rows, float* stats, mm_stream_t s) {
   MM_REQUIRE(sums && stats && rows > 0, "mappo_stats_from_sums: bad args");
   hipLaunchKernelGGL(mm::mappo_stats_from_sums_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, sums, rows, stats);
+  MM_HIP_CHECK(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_mappo_mb_stats(const float* returns, const float* active, const int32_t* chunks, int64_t n_chunks, int32_t L,
+                      int32_t T, int64_t en, double* partial, float* stats, mm_stream_t s) {
+  MM_REQUIRE(returns && active && chunks && partial && stats, "mappo_mb_stats: null pointer");
+  MM_REQUIRE(L > 0 && T > 0 && T % L == 0 && en > 0, "mappo_mb_stats: need L | T");
+  MM_REQUIRE((int64_t)(T / L) * en < (1ll << 31), "mappo_mb_stats: (T / L) * en must be below 2^31");
+  MM_REQUIRE(n_chunks >= 1 && n_chunks <= (int64_t)(T / L) * en, "mappo_mb_stats: need 1 <= n_chunks <= (T / L) * en");
+  const int64_t R = n_chunks * L;
+  const int nb = (int)std::min<int64_t>((n_chunks + 255) / 256, 256);
+  hipLaunchKernelGGL(mm::mappo_mb_moments_kernel, dim3(nb), dim3(256), 0, (hipStream_t)s, returns, active, chunks,
+                     n_chunks, L, en, partial);
+  MM_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(mm::mappo_mb_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, partial, nb, R, stats);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
 }

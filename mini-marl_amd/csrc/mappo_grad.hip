@@ -29,6 +29,8 @@
 // dW1, b1, b2 and the three LayerNorms' parameters. Splitting the MLP backward out of the recurrent pass
 // keeps pass G's registers to its 7 accumulator tiles + the step's GRU state (no spills, 2 waves per SIMD)
 // and drops the parking of the MLP activations the single-pass kernel needed.
+// Minibatch variant (mm_mappo_grad_mb, the *_mb kernels): the same two bodies with IDX = true run over a list of
+// chunks (one PPO minibatch of recurrent_generator's sampler) instead of all of them.
 #include <algorithm>
 
 #include "common.h"
@@ -425,6 +427,13 @@ struct GradArgs {
   float* partial;   // [2][2 NB][pstride]: pass G blocks, then pass M blocks
   int64_t pstride;
 };
+// the minibatch variant's chunk list (native numbering kc * EN + en), a kernel argument of its own: the full-batch
+// kernels keep their argument block
+struct GradArgsMb {
+  GradArgs g;
+  const int32_t* chunks;   // [n_chunks]
+  int64_t n_chunks;
+};
 
 // store an act-frag vector as row `row` of a [rows][32] array: features 8 j + 4 h + 0..3 are 4 consecutive floats
 __device__ __forceinline__ void st_row32(float* base, int64_t row, const float (&v)[16]) {
@@ -777,8 +786,11 @@ struct GruH {
 };
 
 // ---------------------------------------------------------------- pass G: recurrent part
-template <int D, int A, int O, int NA = 1>
-__device__ void gru_body(const GradArgs& k, int net, float* sm) {
+// IDX: tile t's lane ci handles chunk chunks[32 t + ci] of a list of n_chunks instead of chunk 32 t + ci of all
+// (T / L) EN; everything below the chunk number (buffer rows, the dx2 rows written) is the same code.
+template <int D, int A, int O, int NA = 1, bool IDX = false>
+__device__ void gru_body(const GradArgs& k, int net, float* sm, const int32_t* __restrict__ chunks = nullptr,
+                         int64_t n_chunks = 0) {
   using GH = GeoH<D, O>;
   using F = MGeo<D, H, O>;
   const mm_mappo_bwd_args& a = k.a;
@@ -788,7 +800,7 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm) {
   float* S0 = sm + GH::scr + w * GT * TILE;
   float* S1 = S0 + TILE;
   const int L = a.L;
-  const int64_t EN = a.en, nch = (int64_t)(a.T / L) * EN, ntile = (nch + 31) / 32;
+  const int64_t EN = a.en, nch = IDX ? n_chunks : (int64_t)(a.T / L) * EN, ntile = (nch + 31) / 32;
   const int wg = blockIdx.x * GW + w, nwg = gridDim.x * GW;
   float* hs = k.hseq + ((int64_t)net * nwg + wg) * 2 * L * 1024 + lane * 16;   // input hiddens, then x2
   float* xs = hs + L * 1024;
@@ -809,7 +821,9 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm) {
   for (int64_t tile = wg; tile < ntile; tile += nwg) {
     const int64_t c = tile * 32 + ci;
     const bool valid = c < nch;
-    const int64_t cc = valid ? c : 0, kc = cc / EN, en = cc - kc * EN;
+    int64_t cc = valid ? c : 0;
+    if constexpr (IDX) cc = chunks[cc];   // (an invalid lane: the list's first chunk, as chunk 0 without a list)
+    const int64_t kc = cc / EN, en = cc - kc * EN;
     // ---- step 1: forward over the chunk, input hidden of every step kept in the wave scratch
     float hc[16];
     {
@@ -1172,8 +1186,11 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm) {
 // dW2 / db2 / LN2 parameters from d x2 (pass G's output), dx1 = W2^T da2 -> LN1 backward, dW1 / db1, df0 = W1^T da1 ->
 // LN0 parameters. Weight-gradient operands are transposed through 3 LDS tiles per wave (chunks on k); the vector
 // operands of the W^T products take one scale per column (row), those of the weight gradients one per wave tile.
-template <int D, int O, int MWV, int NA = 1>
-__device__ void mlp_body(const GradArgs& k, int net, float* sm) {
+// IDX: the row-steps are the compact range r < n_chunks L over a chunk list, i.e. exactly the buffer rows whose dx2
+// this call's pass G wrote (dx2 stays indexed by buffer row).
+template <int D, int O, int MWV, int NA = 1, bool IDX = false>
+__device__ void mlp_body(const GradArgs& k, int net, float* sm, const int32_t* __restrict__ chunks = nullptr,
+                         int64_t n_chunks = 0) {
   using GM = GeoM<D, O>;
   constexpr bool WIDE = NA > 1;
   using F = MGeo<D, H, O>;
@@ -1186,9 +1203,9 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
   float* S0 = sm + GM::scr + w * MT * TILE;
   float* S1 = S0 + TILE;
   float* S2 = S1 + TILE;
-  const int64_t R = (int64_t)a.T * a.en, ntile = (R + 31) / 32;
+  const int64_t RB = (int64_t)a.T * a.en, R = IDX ? n_chunks * a.L : RB, ntile = (R + 31) / 32;
   const int wg = blockIdx.x * MWV + w, nwg = gridDim.x * MWV;
-  const float* dx2i = k.dx2 + (int64_t)net * R * 32;
+  const float* dx2i = k.dx2 + (int64_t)net * RB * 32;
 
   f32x16 aW2, aW1[DT];
   zero16(aW2);
@@ -1201,7 +1218,15 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm) {
   for (int64_t tile = wg; tile < ntile; tile += nwg) {
     const int64_t r = tile * 32 + ci;
     const bool valid = r < R;
-    const int64_t row = valid ? r : R - 1;
+    int64_t row = valid ? r : R - 1;
+    if constexpr (IDX) {
+      // the list in blocks of EN chunks (the last one shorter), a block's row-steps step-major as in the buffer: the
+      // list of all chunks in native order gives row = r, the full-batch pass's tiles and summation order
+      const int64_t blk = (int64_t)a.L * a.en, bi = row / blk, rem = row - bi * blk;
+      const int64_t m = std::min<int64_t>(a.en, n_chunks - bi * a.en), l = rem / m, e = rem - l * m;
+      const uint32_t c = (uint32_t)chunks[bi * a.en + e], kc = c / (uint32_t)a.en, en = c - kc * (uint32_t)a.en;
+      row = ((int64_t)kc * a.L + l) * a.en + en;
+    }
     const float* smb = sm + opaque0();
     const float* lv = smb + GM::ln0w;
     const float sw = smb[GM::wsc], s_f0 = smb[GM::wsc + 1], s_f1 = smb[GM::wsc + 2];
@@ -1529,6 +1554,15 @@ __global__ __launch_bounds__(64 * GW, 1) void mappo_grad_gru_kernel(GradArgs k) 
     gru_body<D * NA, A, 1, NA>(k, 1, sm);
 }
 
+template <int D, int A, int NA>
+__global__ __launch_bounds__(64 * GW, 1) void mappo_grad_gru_mb_kernel(GradArgsMb k) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  if (blockIdx.y == 0)
+    gru_body<D, A, A, 1, true>(k.g, 0, sm, k.chunks, k.n_chunks);
+  else
+    gru_body<D * NA, A, 1, NA, true>(k.g, 1, sm, k.chunks, k.n_chunks);
+}
+
 // waves per block of pass M: one launch runs both nets, so the fewer of the two images' (a wide critic's 3)
 template <int D, int A, int NA>
 constexpr int mlp_waves() {
@@ -1543,6 +1577,16 @@ __global__ __launch_bounds__((64 * mlp_waves<D, A, NA>()), 1) void mappo_grad_ml
     mlp_body<D, A, MW>(k, 0, sm);
   else
     mlp_body<D * NA, 1, MW, NA>(k, 1, sm);
+}
+
+template <int D, int A, int NA>
+__global__ __launch_bounds__((64 * mlp_waves<D, A, NA>()), 1) void mappo_grad_mlp_mb_kernel(GradArgsMb k) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int MW = mlp_waves<D, A, NA>();
+  if (blockIdx.y == 0)
+    mlp_body<D, A, MW, 1, true>(k.g, 0, sm, k.chunks, k.n_chunks);
+  else
+    mlp_body<D * NA, 1, MW, NA, true>(k.g, 1, sm, k.chunks, k.n_chunks);
 }
 
 // grad[p] = sum over the partials of both passes [b][p], fixed order
@@ -1599,6 +1643,38 @@ struct GradShape {
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
   }
+  // the same three launches over a chunk list (mm_mappo_grad_mb): the same grid, LDS images and scratch layout
+  static int run_mb(const mm_mappo_bwd_args* a, const int32_t* chunks, int64_t n_chunks, const float* ha,
+                    const float* hc, float* ga, float* gc, float* scratch, hipStream_t s) {
+    constexpr size_t lds_g = (size_t)std::max(GeoH<D, A>::total, GeoH<DC, 1>::total) * 4;
+    constexpr size_t lds_m = (size_t)std::max(GeoM<D, A>::total_for(MW), GeoM<DC, 1>::total_for(MW)) * 4;
+    static const int attr_rc = [&]() -> int {
+      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_gru_mb_kernel<D, A, NA>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_grad_mlp_mb_kernel<D, A, NA>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+      return MM_OK;
+    }();
+    if (attr_rc != MM_OK) return attr_rc;
+    GradArgsMb k = {};
+    k.g.a = *a;
+    k.g.h_in[0] = ha;
+    k.g.h_in[1] = hc;
+    k.g.hseq = scratch;
+    k.g.dx2 = scratch + hseq_count(a->L);
+    k.g.partial = k.g.dx2 + 2ll * a->T * a->en * 32;
+    k.g.pstride = pstride();
+    k.chunks = chunks;
+    k.n_chunks = n_chunks;
+    hipLaunchKernelGGL((mappo_grad_gru_mb_kernel<D, A, NA>), dim3(NB, 2), dim3(64 * GW), lds_g, s, k);
+    MM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((mappo_grad_mlp_mb_kernel<D, A, NA>), dim3(NB, 2), dim3(64 * MW), lds_m, s, k);
+    MM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mappo_grad_sum_kernel, dim3((std::max(n0, n1) + 255) / 256, 2), dim3(256), 0, s, k.g.partial,
+                       2 * NB, k.g.pstride, n0, n1, ga, gc);
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
+  }
 };
 
 }  // namespace mgr
@@ -1647,6 +1723,31 @@ int mm_mappo_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const floa
   if (rc != MM_OK) return rc;
 #define MM_CALL(D, N) \
   mm::mgr::GradShape<D, 5, N>::run(a, h_actor, h_critic, grad_actor, grad_critic, scratch, (hipStream_t)s)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  return mm::mappo_dims_error(d);
+}
+
+int mm_mappo_grad_mb(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const int32_t* chunks, int64_t n_chunks,
+                     const float* h_actor, const float* h_critic, float* grad_actor, float* grad_critic,
+                     float* scratch, mm_stream_t s) {
+  MM_REQUIRE(d && a && chunks && h_actor && h_critic && grad_actor && grad_critic && scratch,
+             "mappo_grad_mb: null argument");
+  MM_REQUIRE(a->L > 0 && a->T > 0 && a->T % a->L == 0 && a->en > 0, "mappo_grad_mb: need L | T");
+  MM_REQUIRE((int64_t)(a->T / a->L) * a->en < (1ll << 31), "mappo_grad_mb: (T / L) * en must be below 2^31");
+  MM_REQUIRE(n_chunks >= 1 && n_chunks <= (int64_t)(a->T / a->L) * a->en,
+             "mappo_grad_mb: need 1 <= n_chunks <= (T / L) * en");
+  MM_REQUIRE(a->P[0] && a->P[1] && a->obs && a->mask && a->active && a->act && a->adv && a->old_logp &&
+                 a->old_value && a->returns && a->stats,
+             "mappo_grad_mb: null pointer");
+  MM_REQUIRE(((uintptr_t)h_actor & 15) == 0 && ((uintptr_t)h_critic & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
+             "mappo_grad_mb: hiddens and scratch must be 16-byte aligned");
+  if (!mm::mappo_dims_supported(d)) return mm::mappo_dims_error(d);
+  const int rc = mm::mappo_cent_check(d, a->obs, a->cent_obs, a->en, "mappo_grad_mb");
+  if (rc != MM_OK) return rc;
+#define MM_CALL(D, N)                                                                                             \
+  mm::mgr::GradShape<D, 5, N>::run_mb(a, chunks, n_chunks, h_actor, h_critic, grad_actor, grad_critic, scratch, \
+                                      (hipStream_t)s)
   MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
 #undef MM_CALL
   return mm::mappo_dims_error(d);

@@ -9,7 +9,8 @@ metadata string (component kinds and scalar counters).
 Supported components (``checkpoint_tensors()`` / ``restore_tensors()`` protocol):
   QLearner      behavior [agent | mixer] parameters, target agent / mixer, Adam m / v / step
   OffQMix       behavior + target [agent | mixer], Adam m / v / step
-  MappoTrainer  actor / critic parameters, both Adam states, ValueNorm running statistics
+  MappoTrainer  actor / critic parameters, both Adam states, ValueNorm running statistics; scalar: the number of
+                train() calls (seeds the minibatch permutations; 0 when absent)
 """
 import json
 

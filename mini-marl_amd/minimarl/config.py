@@ -88,13 +88,15 @@ def qmix_reference():
 
 @dataclass
 class MappoTrainConfig:
-    """mappo/_config.py values on the hot path (rmappo, shared policy, recurrent, 1 minibatch)."""
+    """mappo/_config.py values on the hot path (rmappo, shared policy, recurrent chunks; train_batch_size PPO
+    minibatches per epoch = MappoTrainer / MappoRunner num_mini_batch)."""
     n_envs: int = 4096
     n_agents: int = 8
     episode_length: int = 100
     hidden: int = 32
     data_chunk_length: int = 5
     ppo_epoch: int = 15
+    train_batch_size: int = 1          # the reference's name for the number of minibatches per epoch
     clip_param: float = 0.2
     huber_delta: float = 10.0
     entropy_coef: float = 0.01

@@ -7,9 +7,13 @@ include/minimarl.h (csrc/mappo.hip). Everything runs on the GPU; there is no CPU
 
 Deviations: E independent envs instead of one env stepped E times per timestep
 (magym_runner.py:53-54); the rollout's Categorical sample uses the device counter RNG
-(inverse CDF); the one PPO minibatch per epoch (train_batch_size 1) is processed in chunk
-order instead of a torch.randperm order (a full-batch gradient: same value up to float
-summation order, pinned by tests/test_mappo_oracle.py::test_ppo_train_golden[False]).
+(inverse CDF). PPO minibatches (train_batch_size = num_mini_batch, ramppo_network.py:245-271): with one
+minibatch per epoch the chunks are processed in chunk order instead of a torch.randperm order (a
+full-batch gradient: same value up to float summation order, pinned by
+tests/test_mappo_oracle.py::test_ppo_train_golden[False]); with more, each epoch draws one permutation
+of the chunks and takes num_mini_batch steps on its slices, the remainder chunks dropped, as the
+reference's recurrent_generator does (shared_buffer.py:318-331) -- drawn by a device generator, since
+torch's CPU randperm stream is not the device's (a recorded one replays through train(perms=...)).
 """
 import ctypes
 
@@ -243,17 +247,52 @@ class MappoBuffer:
                                  stream_handle(self.device)), "mappo_gae")
 
 
+def chunks_ref_to_native(c, T, L, EN):
+    """Chunk numbers of the reference's recurrent_generator (c = en * (T / L) + kc: the buffer cast to
+    [E, N, T] and cut every L steps, shared_buffer.py:325-357) -> the buffer's native numbering kc * EN + en
+    (include/minimarl.h mm_mappo_grad_mb). c: an integer numpy array or torch tensor."""
+    K = int(T) // int(L)
+    return (c % K) * int(EN) + c // K
+
+
+def chunks_native_to_ref(c, T, L, EN):
+    """The inverse of chunks_ref_to_native."""
+    K = int(T) // int(L)
+    return (c % int(EN)) * K + c // int(EN)
+
+
 class MappoTrainer:
-    """R_MAPPO (ramppo_network.py:9-287) with train_batch_size 1, recurrent chunks of L steps."""
+    """R_MAPPO (ramppo_network.py:9-287): train_batch_size = num_mini_batch, recurrent chunks of L steps."""
 
     def __init__(self, policy, T, EN, L=5, ppo_epoch=15, clip_param=0.2, huber_delta=10.0, entropy_coef=0.01,
                  value_loss_coef=0.5, max_grad_norm=0.5, actor_lr=1e-4, critic_lr=1e-4, opti_eps=1e-5,
-                 grad_allreduce=None, fused=True):
+                 grad_allreduce=None, fused=True, num_mini_batch=1, perm_seed=0):
         """fused: one mm_mappo_grad pass per epoch (forward recomputed in the backward, weight gradients
         reduced on MFMA in the same kernel); False: the TRAIN forward with saved activations, the BPTT
-        kernel writing per-row operands and the separate weight-gradient reduction."""
+        kernel writing per-row operands and the separate weight-gradient reduction.
+
+        num_mini_batch M (the reference's train_batch_size): 1 = one full-batch step per epoch in chunk order;
+        M > 1 = per epoch one permutation of the T * EN / L chunks, M steps on its slices of
+        (T * EN / L) // M chunks (mm_mappo_mb_stats + mm_mappo_vn_update + mm_mappo_grad_mb + mm_clip_adam each),
+        the remainder dropped. perm_seed seeds the device generator of those permutations together with the
+        number of train() calls so far and the epoch."""
         assert T % L == 0, "episode length must be a multiple of data_chunk_length"
         self.fused = bool(fused)
+        self.M, self.perm_seed, self.train_calls = int(num_mini_batch), int(perm_seed), 0
+        self.n_chunks = int(T) * int(EN) // int(L)
+        self.mbs = self.n_chunks // max(self.M, 1)
+        if self.M < 1:
+            raise ValueError(f"num_mini_batch={num_mini_batch} must be at least 1")
+        if self.M > 1:
+            if not self.fused:
+                raise NotImplementedError(f"num_mini_batch={self.M} needs fused=True: only the fused gradient pass "
+                                          "(mm_mappo_grad_mb) runs over a chunk list, the saves + wgrad path does not")
+            if grad_allreduce is not None:
+                raise NotImplementedError(f"num_mini_batch={self.M} with grad_allreduce: the per-minibatch statistics "
+                                          "(active count, return moments) would need their own all-reduce")
+            if self.mbs < 1:
+                raise NotImplementedError(f"num_mini_batch={self.M} exceeds the {self.n_chunks} chunks of the buffer "
+                                          f"(T={T} x EN={EN} / L={L}): a minibatch would hold no chunk")
         if not self.fused and policy.cent_agents:
             raise NotImplementedError(f"fused=False does not support a centralized critic (cent_agents="
                                       f"{policy.cent_agents}, critic input width {policy.Dc}): only the fused "
@@ -288,7 +327,8 @@ class MappoTrainer:
         self.v = [torch.zeros_like(n.flat) for n in nets]
         self.step = [torch.zeros(1, device=dev) for _ in nets]
         self.norm_part = [torch.zeros(256, device=dev) for _ in nets]
-        self.norms = torch.zeros(2, max(1, self.epochs), device=dev)
+        self.norms = torch.zeros(2, max(1, self.epochs * self.M), device=dev)
+        self.perm_gen = torch.Generator(device=dev) if self.M > 1 else None
         self.vn = torch.zeros(3, device=dev)          # ValueNorm running mean, mean sq, debias (f32)
         self.stats = torch.zeros(8, device=dev)
         self.adv = torch.zeros(self.rows, device=dev)
@@ -300,7 +340,9 @@ class MappoTrainer:
         ts = {"actor": self.p.actor.flat, "critic": self.p.critic.flat, "vn": self.vn}
         for n in (0, 1):
             ts[f"m{n}"], ts[f"v{n}"], ts[f"step{n}"] = self.m[n], self.v[n], self.step[n]
-        return ts, {}
+        # (the number of train() calls seeds the minibatch permutations: a resumed run draws what the uninterrupted
+        # run would have drawn)
+        return ts, {"train_calls": self.train_calls}
 
     def restore_tensors(self, ts, scalars):
         from .checkpoint import copy_into
@@ -322,6 +364,7 @@ class MappoTrainer:
             copy_into(self.m[n], ts[f"m{n}"], f"m{n}")
             copy_into(self.v[n], ts[f"v{n}"], f"v{n}")
             copy_into(self.step[n], ts[f"step{n}"], f"step{n}")
+        self.train_calls = int((scalars or {}).get("train_calls", 0))   # (absent in older files)
 
     # -- ValueNorm (utils/valuenorm.py) ------------------------------------------------------
     def value_normalizer_state(self):
@@ -404,34 +447,105 @@ class MappoTrainer:
         if self.allreduce is not None:
             for n in (0, 1):
                 self.allreduce(self.grad[n])
+        self.clip_adam(ep % self.norms.shape[1], scale)
+
+    def clip_adam(self, slot, scale=1.0):
+        """clip_grad_norm_ + Adam of both nets on self.grad; the pre-clip norms go to self.norms[:, slot]."""
+        L_, s = lib(), stream_handle(self.device)
         nets = (self.p.actor, self.p.critic)
         for n in (0, 1):
             check(L_.mm_clip_adam(ptr(nets[n].flat), ptr(self.grad[n]), ptr(self.m[n]), ptr(self.v[n]),
                                   nets[n].total, nets[n].total, self.max_norm, self.lrs[n], 0.9, 0.999, self.eps,
-                                  ptr(self.step[n]), ptr(self.norm_part[n]), ptr(self.norms[n, ep % self.norms.shape[1]]),
+                                  ptr(self.step[n]), ptr(self.norm_part[n]), ptr(self.norms[n, slot]),
                                   scale, s), "clip_adam")
 
-    def train(self, buf):
-        self.prepare(buf)
-        fa, ba = self.fwd_args(buf), self.bwd_args(buf)
+    # -- minibatches (num_mini_batch > 1) ------------------------------------------------------
+    def draw_perms(self, call=None):
+        """The permutations train() call number ``call`` (default: the next one) uses, [epochs, n_chunks] int64 on
+        the device in the reference's chunk numbering: one torch.randperm per epoch from the device generator
+        seeded by (perm_seed, call, epoch)."""
+        call = self.train_calls if call is None else int(call)
+        rows = []
         for ep in range(self.epochs):
-            self.epoch(buf, ep, fa, ba)
+            self.perm_gen.manual_seed(((self.perm_seed * 1000003 + call) * 1000003 + ep) & (2 ** 63 - 1))
+            rows.append(torch.randperm(self.n_chunks, generator=self.perm_gen, device=self.device))
+        return torch.stack(rows) if rows else torch.zeros(0, self.n_chunks, dtype=torch.int64, device=self.device)
+
+    def native_chunks(self, perms):
+        """Injected permutations ([epochs, n_chunks], the reference's numbering: a recorded torch.randperm), checked
+        on the host -> the device int32 chunk lists in the native numbering."""
+        pm = np.asarray(perms.detach().cpu() if torch.is_tensor(perms) else perms)
+        if pm.shape != (self.epochs, self.n_chunks) or pm.dtype.kind not in "iu":
+            raise ValueError(f"perms: expected integers of shape [epochs={self.epochs}, n_chunks={self.n_chunks}], "
+                             f"got {pm.dtype} {tuple(pm.shape)}")
+        want = np.arange(self.n_chunks)
+        for ep in range(self.epochs):
+            if not np.array_equal(np.sort(pm[ep].astype(np.int64)), want):
+                raise ValueError(f"perms[{ep}] is not a permutation of the {self.n_chunks} chunks")
+        return self._to_native(torch.as_tensor(pm.astype(np.int64), device=self.device))
+
+    def _to_native(self, perms):
+        return chunks_ref_to_native(perms, self.T, self.L, self.EN).to(torch.int32).contiguous()
+
+    def mb_stats(self, buf, chunks):
+        """The minibatch's active count and return moments into self.stats (chunks: device int32, native)."""
+        check(lib().mm_mappo_mb_stats(ptr(buf.returns), ptr(buf.active_masks), ptr(chunks), int(chunks.numel()),
+                                      self.L, self.T, self.EN, ptr(self.adv_part), ptr(self.stats),
+                                      stream_handle(self.device)), "mappo_mb_stats")
+
+    def gradients_mb(self, buf, chunks, ba=None):
+        """gradients() over the chunks of one minibatch (device int32, native numbering)."""
+        ba = ba or self.bwd_args(buf)
+        check(lib().mm_mappo_grad_mb(ctypes.byref(self.p.dims), ctypes.byref(ba), ptr(chunks), int(chunks.numel()),
+                                     ptr(buf.rnn_states), ptr(buf.rnn_states_critic), ptr(self.grad[0]),
+                                     ptr(self.grad[1]), ptr(self.gscr), stream_handle(self.device)), "mappo_grad_mb")
+
+    def minibatch(self, buf, chunks, slot, ba=None):
+        """One ppo_update (ramppo_network.py:56-209) on a minibatch: its moments, ValueNorm.update(return_batch),
+        the gradients over its chunks, clip + Adam."""
+        self.mb_stats(buf, chunks)
+        check(lib().mm_mappo_vn_update(ptr(self.vn), ptr(self.stats), 0.99999, stream_handle(self.device)),
+              "mappo_vn_update")
+        self.gradients_mb(buf, chunks, ba)
+        self.clip_adam(slot)
+
+    def train(self, buf, perms=None):
+        """R_MAPPO.train (ramppo_network.py:211-287). perms (num_mini_batch > 1 only): [epochs, n_chunks]
+        permutations in the reference's chunk numbering c = en * (T / L) + kc replacing the drawn ones."""
+        if self.M == 1:
+            if perms is not None:
+                raise ValueError("perms needs num_mini_batch > 1: one minibatch per epoch holds every chunk, in "
+                                 "chunk order")
+            self.prepare(buf)
+            fa, ba = self.fwd_args(buf), self.bwd_args(buf)
+            for ep in range(self.epochs):
+                self.epoch(buf, ep, fa, ba)
+        else:
+            native = self._to_native(self.draw_perms()) if perms is None else self.native_chunks(perms)
+            self.prepare(buf)
+            ba = self.bwd_args(buf)
+            for ep in range(self.epochs):
+                for i in range(self.M):
+                    self.minibatch(buf, native[ep, i * self.mbs:(i + 1) * self.mbs], ep * self.M + i, ba)
+        self.train_calls += 1
         return self.train_info()
 
     def train_info(self):
         la = self.loss_acc.detach().cpu().numpy().astype(np.float64)
         nrm = self.norms.detach().cpu().numpy().astype(np.float64)
-        e = max(1, self.epochs)
+        e = max(1, self.epochs * self.M)                                        # updates
+        rows = self.rows if self.M == 1 else self.mbs * self.L                  # rows trained per update
         return {"value_loss": la[MM_MLOSS_VALUE] / e, "policy_loss": la[MM_MLOSS_POLICY] / e,
                 "dist_entropy": la[MM_MLOSS_ENTROPY] / e, "actor_grad_norm": nrm[0].mean(),
-                "critic_grad_norm": nrm[1].mean(), "ratio": la[MM_MLOSS_RATIO] / (e * self.rows)}
+                "critic_grad_norm": nrm[1].mean(), "ratio": la[MM_MLOSS_RATIO] / (e * rows)}
 
 
 class MappoRunner:
     """MAGYM_Runner (magym_runner.py:30-195) on lockstep device envs: collect -> insert -> compute -> train."""
 
     def __init__(self, env, policy, T=100, L=5, ppo_epoch=15, gamma=0.99, gae_lambda=0.95, seed=0,
-                 grad_allreduce=None):
+                 grad_allreduce=None, num_mini_batch=1):
+        """num_mini_batch: PPO minibatches per epoch (MappoTrainer; their permutations are seeded with ``seed``)."""
         self.env, self.p = env, policy
         if policy.cent_agents not in (None, env.N):
             raise ValueError(f"policy.cent_agents={policy.cent_agents} != the env's {env.N} agents")
@@ -439,7 +553,8 @@ class MappoRunner:
         self.T, self.gamma, self.gl = int(T), gamma, gae_lambda
         dev = self.device = policy.device
         self.buf = MappoBuffer(T, self.E, self.N, self.D, policy.H, dev)
-        self.trainer = MappoTrainer(policy, T, self.E * self.N, L, ppo_epoch, grad_allreduce=grad_allreduce)
+        self.trainer = MappoTrainer(policy, T, self.E * self.N, L, ppo_epoch, grad_allreduce=grad_allreduce,
+                                    num_mini_batch=num_mini_batch, perm_seed=int(seed))
         self.seed = int(seed)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.done = torch.zeros(self.E, dtype=torch.uint8, device=dev)

@@ -1,8 +1,9 @@
 """MAPPO phase timing at BASELINE config 3 (4096 envs x 8 agents, T=100, L=5, 15 PPO epochs).
 
-usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n] [--centralized-v]
+usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n] [--centralized-v] [--minibatches M]
 Prints one JSON line: ms per rollout step, per compute (values + GAE), per train() and per epoch (medians over the
 timed episodes; the first episode is warm-up). --centralized-v: the critic reads the env's share_obs.
+--minibatches M: M PPO minibatches per epoch (num_mini_batch; an epoch is then M updates on 1 / M of the chunks each).
 """
 import argparse
 import json
@@ -27,10 +28,11 @@ def main():
     ap.add_argument("--epochs", type=int, default=15)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--centralized-v", action="store_true", help="centralized critic (use_centralized_V)")
+    ap.add_argument("--minibatches", type=int, default=1, help="PPO minibatches per epoch (num_mini_batch)")
     a = ap.parse_args()
     env = VecEnv(a.envs, a.agents, max_steps=100, device="cuda")
     p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0, **({"cent_agents": a.agents} if a.centralized_v else {}))
-    r = MappoRunner(env, p, T=a.T, L=5, ppo_epoch=a.epochs, seed=1)
+    r = MappoRunner(env, p, T=a.T, L=5, ppo_epoch=a.epochs, seed=1, num_mini_batch=a.minibatches)
     r.warmup()
     ev = lambda: torch.cuda.Event(enable_timing=True)
     res = []
@@ -51,6 +53,7 @@ def main():
     epi = med([sum(x) for x in res])   # (the median episode, not the sum of the phase medians)
     rows = a.envs * a.agents * a.T
     out = {"envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs, "centralized_v": bool(a.centralized_v),
+           "minibatches": a.minibatches, "train_ms_per_update": tr / (a.epochs * a.minibatches),
            "episodes": len(res),
            "rollout_ms_per_step": ro / a.T, "compute_ms": co, "train_ms": tr, "train_ms_per_epoch": tr / a.epochs,
            "episode_ms": epi, "agent_env_steps_per_s_incl_train": rows / (epi / 1e3),
