@@ -284,8 +284,13 @@ int mm_rollout_step(mm_env* env, const mm_qnet_dims* d, const float* packed_t, c
  * mm_env_get_state_buf), arrival ticket — zero-initialised once, then owned by these launches.
  * handoff = int64 [T][handoff_len][N][32], T = ceil(E / 256), handoff_len >= n_steps, zero-initialised: word w of
  * (tile, launch step, agent) = (low 32 bits of the launch sequence + 1) << 32 | the 4-bit actions of the tile's envs
- * 8 w .. 8 w + 7. Supported when mm_rollout_chunk_supported() != 0 (the fused step's geometry and 2 N T blocks <= the
- * device's CUs: all blocks must be co-resident; a hand-off wait longer than 20 ms sets bit 1 of *err and proceeds). */
+ * 8 w .. 8 w + 7. A block on the fp16x3 image runs its 256 envs as four independent 64-env groups (envs 64 j ..
+ * 64 j + 63 = words 8 j .. 8 j + 7 of each agent): a group waits only for its own N x 8 words of the step and for its
+ * own block-local counters, never for the rest of the block, so the groups of a tile run up to a launch apart (slot
+ * i of handoff_len >= n_steps is written once per launch). A block on the exact-f32 image (range-guarded agent) steps
+ * block-synchronously and publishes its 32 words together. Supported when mm_rollout_chunk_supported() != 0 (the fused
+ * step's geometry and 2 N T blocks <= the device's CUs: all blocks must be co-resident; a hand-off or group wait
+ * longer than 20 ms sets bit 1 of *err and proceeds). */
 typedef struct mm_rollout_chunk_io {
   float* store_obs; int64_t row_stride; int64_t n_rows;
   const int64_t* staging; int64_t* cur_row;

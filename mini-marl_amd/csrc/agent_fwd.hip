@@ -31,7 +31,7 @@ struct QFwdParams {
   const float* packed;
   int E, N, D, A;
   int nblocks;  // blocks of this net inside a (possibly dual) launch
-  int stagger;  // fp16x3 kernel: waves 8-15 start stagger x s_sleep(8) late
+  int stagger;  // fp16x3 kernel: waves 8-15 start stagger x s_sleep(8) late (not the chunk kernel: its groups drift)
   int dbg;      // unused (kept for the kernarg layout)
   int pad_;
 };
@@ -1923,6 +1923,12 @@ __global__ __launch_bounds__(1024, 1) void rollout_step_kernel(QFwdParams p0, QF
 //       writer block (target net, agent 0) writes rew / done of step t into their ring positions and cur_row;
 //   (5) every wave: the forward (target on s'_t -> max Q'_t, storing s'_t into slot c + 1; behavior on s_{t+1}
 //       -> act / Q(a) of step t + 1 into their ring positions); behavior blocks then publish their actions.
+// A block on the fp16x3 image runs these steps as four independent 64-env groups (rollout_env.h: group j = waves
+// 4j .. 4j + 3 = the envs those waves own in the forward), with no block barrier in the step loop: the group's
+// dynamics wave polls the group's N x 8 hand-off words and runs (2) and (4) 64 lanes wide, and the group's waves
+// meet through LDS counters (grp_arrive / grp_wait: reads of step i - 1 done, dynamics of step i done, and around
+// the slot-0 stores of a chunk start), so one group's forward runs under another's wait and dynamics. A block on
+// the exact-f32 image keeps the block-synchronous loop described above.
 // The TD / chunk-store fold of the launch's steps runs afterwards (mm_td_fold_range). Blocks are mapped so that a
 // tile's 2N blocks share an XCD (blocks b, b + 8, ... share one: MI355X_MICROARCH.md "Workgroup dispatch"), which
 // keeps the hand-off in one L2 — a speed choice only, correctness never depends on placement. All blocks must be
@@ -1967,6 +1973,7 @@ struct ChunkCtx {
   uint16_t* ssa;      // [2][256] steps, apples of the env
   uint8_t* sdone;     // [2][256] dones by step parity
   uint8_t* shx;       // [256] the exact-body behavior block's outgoing actions; at the loop top [N][32] u32 hand-off words
+  uint32_t* sgrp;     // [kRollGroups][kRollGroupCtrs] group counters of the fp16x3 loop (grp_arrive / grp_wait)
   uint64_t ctr0, seq;
   float eps;
   int tile, agent, e0;
@@ -1996,6 +2003,7 @@ __device__ __forceinline__ ChunkCtx chunk_ctx(const QFwdParams* kargs) {
   cx.ssa = reinterpret_cast<uint16_t*>(envl + lay.ssa);
   cx.sdone = reinterpret_cast<uint8_t*>(envl + lay.sdone);
   cx.shx = reinterpret_cast<uint8_t*>(envl + lay.shx);
+  cx.sgrp = reinterpret_cast<uint32_t*>(envl + lay.sgrp);
   // (the last block rewrites these only after every block has finished: constant for the launch)
   cx.ctr0 = *rc.counter;
   cx.seq = *rc.seq;
@@ -2003,13 +2011,47 @@ __device__ __forceinline__ ChunkCtx chunk_ctx(const QFwdParams* kargs) {
   return cx;
 }
 
-// timing stamp k of step i of waves 0 and 15 (lane 0; MM_ROLL_DEBUG builds only)
+// Group synchronisation of the fp16x3 step loop: monotonically increasing 32-bit counters in LDS, no block barrier.
+// A wave arrives once its own LDS accesses so far have completed (one lane's ds_add after s_waitcnt lgkmcnt(0); the
+// LDS serves a wave's instructions in order, so whoever sees the count sees the data). A waiter spins with s_sleep
+// until the counter reaches the step's target; like the hand-off poll the spin is bounded by kHandoffTimeout
+// (error bit 1, then the wave goes on), so a grid that is not co-resident still drains.
+typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+__device__ __forceinline__ void grp_arrive(uint32_t* ctr, int lane) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if (lane == 0) __hip_atomic_fetch_add((lds_u32_t*)ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  asm volatile("" ::: "memory");
+}
+__device__ __forceinline__ void grp_wait(uint32_t* ctr, uint32_t target, uint32_t* err, int lane) {
+  auto seen = [&]() {
+    return __builtin_amdgcn_readfirstlane(
+               __hip_atomic_load((lds_u32_t*)ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= target;
+  };
+  if (!seen()) {
+    const uint64_t tw = __builtin_amdgcn_s_memrealtime();
+    while (true) {
+      __builtin_amdgcn_s_sleep(1);
+      if (seen()) break;
+      if (__builtin_amdgcn_s_memrealtime() - tw > kHandoffTimeout) {
+        if (lane == 0) atomicOr(err, 2u);
+        break;
+      }
+    }
+  }
+  asm volatile("" ::: "memory");
+}
+
+// timing stamp k of step i (lane 0; MM_ROLL_DEBUG builds only) of two waves per group of the behavior blocks: the
+// group's dynamics wave (slot 0) and one other wave (slot 1), steps 0-11:
+// trace[((((tile N + agent) 4 + group) 2 + slot) 12 + i) 4 + k]
 #if MM_ROLL_DEBUG
 #define MM_CSTAMP(k)                                                                                          \
   do {                                                                                                        \
-    if (rc.trace && lane == 0 && i < 16 && (wave == 0 || wave == 15)) {                                       \
-      const int lbk = cx.tile * 2 * N + (second ? N : 0) + agent;                                             \
-      rc.trace[(((int64_t)lbk * 2 + (wave ? 1 : 0)) * 16 + i) * 4 + (k)] = __builtin_amdgcn_s_memrealtime();  \
+    if (rc.trace && lane == 0 && i < 12 && second) {                                                          \
+      const int gj = roll_group_of_wave(wave);                                                                \
+      const int ws = wave == roll_group_dyn_wave(gj) ? 0 : (wave == 4 * gj + ((gj + 1) & 3) ? 1 : -1);         \
+      const int64_t ix = (((((int64_t)cx.tile * N + agent) * 4 + gj) * 2 + ws) * 12 + i) * 4 + (k);           \
+      if (ws >= 0 && ix < 60000) rc.trace[ix] = __builtin_amdgcn_s_memrealtime();                             \
     }                                                                                                         \
   } while (0)
 #else
@@ -2058,8 +2100,13 @@ __device__ __forceinline__ void roll_chunk_steps() {
   const mm_qfwd_io& io = p.io;
   const int tile = cx.tile, agent = cx.agent, e0 = cx.e0;
   const bool second = cx.second, writer = cx.writer;
-  const int le_d = tx, de = e0 + le_d;
-  const bool dvalid = tx < 256 && de < E;
+  // dynamics lanes: exact body waves 0-3, lane tx <-> env tx of the tile; fp16x3 body the group's dynamics wave,
+  // lane l <-> env 64 j + l (all 64 lanes of one wave per group)
+  const int grp = roll_group_of_wave(wave);
+  const bool dynw = EXACT ? tx < 256 : wave == roll_group_dyn_wave(grp);
+  uint32_t* gc = cx.sgrp + kRollGroupCtrs * grp;   // the group's counters (fp16x3 body)
+  const int le_d = EXACT ? tx : roll_group_env0(grp) + lane, de = e0 + le_d;
+  const bool dvalid = dynw && de < E;
   uint32_t* rows = cx.sgrid + le_d * roll_gbw(R);
   const int le = wave * 16 + (lane & 15), e = e0 + le;           // fp16x3 body / begin-store lane mapping
   const int l32 = wave * 32 + (lane & 31), e32 = e0 + l32;       // exact body lane mapping (waves 0-7)
@@ -2067,9 +2114,11 @@ __device__ __forceinline__ void roll_chunk_steps() {
     // writes staging set (set0 + k) % S), ring position of the step (rings of RL steps hold rewards / dones / max Q' /
     // actions / Q(a) by step)
     int c = rc.c0 + i, kset = rc.set0;
+    uint32_t kcs = rc.c0 == 0 ? 1u : 0u;   // chunk starts of the launch up to and including step i
     while (c >= CL) {
       c -= CL;
       kset = kset + 1 == rc.S ? 0 : kset + 1;
+      ++kcs;
     }
     const int64_t* stg = rc.staging + (int64_t)kset * E;
     const int pos = rc.pos0 + i >= rc.RL ? rc.pos0 + i - rc.RL : rc.pos0 + i;
@@ -2077,9 +2126,57 @@ __device__ __forceinline__ void roll_chunk_steps() {
     const uint64_t ctr = cx.ctr0 + (uint64_t)i;
     const int cur = i & 1, prv = cur ^ 1;
     MM_CSTAMP(0);
+    // (the group's dynamics chain at the top issue priority: its three other waves wait for it)
+    // (s_setprio ignores EXEC, so the role test has to be a scalar branch: the wave index through readfirstlane.
+    // The group's other waves keep their last forward's priority while they spin)
+    if (!EXACT &&
+        __builtin_amdgcn_readfirstlane(wave) == roll_group_dyn_wave(__builtin_amdgcn_readfirstlane(grp)))
+      __builtin_amdgcn_s_setprio(3);
     // (1) the actions of step t (i > 0: published by the tile's N behavior blocks at the end of their step t - 1)
     uint32_t aq[2] = {0u, 0u};   // 4-bit actions, agent k at bits 4 (k & 7) of aq[k >> 3]
     if (i > 0) {
+      if constexpr (!EXACT) {
+        if (dynw) {
+          // the group's N x 8 hand-off words of step i (words 8 j .. 8 j + 7 of each agent's 32), polled by the
+          // group's dynamics wave as below; their action halves into the group's slice of shx
+          const int w0 = roll_group_word0(grp);
+          const uint64_t* hs = rc.hx + ((int64_t)tile * rc.hxl + i) * N * 32 + w0;
+          uint32_t* hl = reinterpret_cast<uint32_t*>(cx.shx) + w0;
+          const uint32_t tag = (uint32_t)cx.seq + 1u;
+          constexpr int NQ = (kRollMaxN * 8 + 63) / 64;
+          const int nw = N * 8;
+          int wo[NQ];          // word q * 64 + lane = (agent k, word w) -> offset 32 k + w
+          uint32_t got = 0u;   // bit q: word q * 64 + lane received (or outside the N x 8 words)
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) {
+            const int ix = q * 64 + lane;
+            wo[q] = (ix >> 3) * 32 + (ix & 7);
+            if (ix >= nw) got |= 1u << q;
+          }
+          const uint32_t need = (1u << NQ) - 1u;
+          const uint64_t tw = __builtin_amdgcn_s_memrealtime();
+          while (true) {
+            uint64_t w[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+              if (!((got >> q) & 1u)) w[q] = __hip_atomic_load(hs + wo[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+              if (!((got >> q) & 1u) && (uint32_t)(w[q] >> 32) == tag) {
+                hl[wo[q]] = (uint32_t)w[q];
+                got |= 1u << q;
+              }
+            if (__all(got == need)) break;
+            __builtin_amdgcn_s_sleep(1);
+            if (__builtin_amdgcn_s_memrealtime() - tw > kHandoffTimeout) {
+              if (lane == 0) atomicOr(rc.err, 2u);
+              break;
+            }
+          }
+          // (a) the group's four waves are past their reads of the LDS env state of step i - 1
+          grp_wait(gc + 0, 4u * (uint32_t)i, rc.err, lane);
+        }
+      } else {
       __syncthreads();   // every wave is past its reads of the LDS env state of step i - 1
       if (wave == 0) {
         // the tile's N x 32 hand-off words of step i, polled by wave 0 until each carries this launch's tag (tag and
@@ -2115,6 +2212,7 @@ __device__ __forceinline__ void roll_chunk_steps() {
         }
       }
       __syncthreads();
+      }
       MM_CSTAMP(1);
       if (dvalid) {
         const uint32_t* hl = reinterpret_cast<const uint32_t*>(cx.shx) + (le_d >> 3);
@@ -2143,15 +2241,26 @@ __device__ __forceinline__ void roll_chunk_steps() {
       }
     }
     // (3) chunk start: slot 0 of the staging rows <- s_t (lane (env, g) writes features 16 q + 4 g .. + 3)
+    // (fp16x3 body: (c) the group's waves wait for the reset above, and its dynamics wave for their stores' reads)
     if (c == 0) {
-      __syncthreads();
+      if constexpr (EXACT) {
+        __syncthreads();
+      } else {
+        if (dynw) grp_arrive(gc + 2, lane);
+        grp_wait(gc + 2, kcs, rc.err, lane);
+      }
       if (!second && e < E) {
         const int64_t srb = stg[e];
         if (srb >= 0 && srb < rc.n_rows)
           roll_store_slot0(cx.sgrid + le * roll_gbw(R), cx.spq[le * N + agent] & 0xFF, cx.stab, R,
                            rc.store_obs + srb * rc.row_stride + (int64_t)agent * D, D, lane >> 4);
       }
-      __syncthreads();
+      if constexpr (EXACT) {
+        __syncthreads();
+      } else {
+        grp_arrive(gc + 3, lane);
+        if (dynw) grp_wait(gc + 3, 4u * kcs, rc.err, lane);
+      }
     }
     // (4) the env dynamics of step t (rollout_step_kernel's loop; positions / counters from LDS)
     if (dvalid) {
@@ -2196,7 +2305,14 @@ __device__ __forceinline__ void roll_chunk_steps() {
         rc.cur_row[de] = dn ? -1 : myrow;
       }
     }
-    __syncthreads();
+    if constexpr (EXACT) {
+      __syncthreads();
+    } else {   // (b) the group's dynamics of step i are done
+      if (dynw)
+        grp_arrive(gc + 1, lane);
+      else
+        grp_wait(gc + 1, (uint32_t)i + 1u, rc.err, lane);
+    }
     MM_CSTAMP(2);
     // (5) the forward: target on s'_t (max Q'_t, s'_t stored into slot c + 1), behavior on s_{t+1} (act / Q(a))
     const int64_t off = (int64_t)(second ? posn : pos) * EN;
@@ -2250,6 +2366,9 @@ __device__ __forceinline__ void roll_chunk_steps() {
       const int rcw = cx.spq[ls * N + agent] & 0xFF;
       const uint64_t wd = roll_obs_word_g(cx.sgrid + ls * roll_gbw(R), R, rcw >> 4, rcw & 15, g);
       const float cr = cx.stab[rcw >> 4], cc = cx.stab[R + (rcw & 15)];
+      // (a) this wave's reads of the step's LDS env state are done (dones, position word, obs rows; the forward
+      // reads the weight image only): the group's dynamics of step i + 1 may run under this forward
+      grp_arrive(gc + 0, lane);
       auto ol = [&](int kb, float (&x)[8]) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -2263,8 +2382,15 @@ __device__ __forceinline__ void roll_chunk_steps() {
       };
       float xn[8];
       ol(0, xn);
-      if (wave >= 8)
-        for (int s = 0; s < p.stagger; ++s) __builtin_amdgcn_s_sleep(8);
+      // issue priority of this forward: (group + step) mod 4, so the four waves a SIMD carries (one per group) rank
+      // differently every step. With equal priorities the oldest wave wins the SIMD: group 0 then steps every 13 us
+      // and group 3 every 21 us, and the launch ends on group 3 alone (four-group chunk loop)
+      switch (__builtin_amdgcn_readfirstlane((grp + i) & 3)) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+      }
       // (the image base offset by the per-step opaque zero: the fragment addresses are formed inside the step,
       // not hoisted out of the loop into registers that then spill)
       const int a = agent_q_fwd_body_h3<F1, G, H, AB>(p, agent, e, wsm_ptr() + tz, ol, xn, h0, cx.eps, ctr, off, 1,
@@ -2295,6 +2421,8 @@ __device__ __forceinline__ void roll_chunk_steps() {
       }
     }
   }
+  // the fp16x3 groups end their last step at different times: the epilogue reads every group's final env state
+  if constexpr (!EXACT) __syncthreads();
 }
 
 template <int F1, int G, int H, int AB>
@@ -2343,6 +2471,7 @@ __global__ __launch_bounds__(1024, 1) void rollout_chunk_kernel(QFwdParams p0, Q
   } else if (threadIdx.x < 256) {
     cx.sdone[256 + le_d] = 0;
   }
+  if (threadIdx.x >= 512 && threadIdx.x < 512 + kRollGroups * kRollGroupCtrs) cx.sgrp[threadIdx.x - 512] = 0u;
   __syncthreads();
 
   // (two loops, one per body: the exact-f32 loop's spills stay in that rare path — the fp16x3 loop's spill code is

@@ -32,10 +32,20 @@ __host__ __device__ __forceinline__ RollLds roll_lds(int R, int C, int N) {
   return m;
 }
 // The chunk kernel's LDS after the weight image: coordinate features, nibble-row grids, 16-bit position words
-// (prev_r, prev_c, r, c), dones by step parity, the behavior block's outgoing actions
+// (prev_r, prev_c, r, c), dones by step parity, the behavior block's outgoing actions, the group counters
 struct RollChunkLds {
-  int stab, sgrid, spq, ssa, sdone, shx, total;
+  int stab, sgrid, spq, ssa, sdone, shx, sgrp, total;
 };
+// The fp16x3 step loop runs a block's 256 envs as kRollGroups independent groups of 64: group j is waves 4j .. 4j + 3
+// and envs 64j .. 64j + 63 of the tile (the envs those waves own in the forward), words 8j .. 8j + 7 of each agent's
+// 32 hand-off words. One wave of the group runs its env dynamics, 64 lanes wide: wave 4j + j, so that the four
+// groups' dynamics chains sit on four different SIMDs (wave w runs on SIMD w mod 4).
+static constexpr int kRollGroups = 4;
+static constexpr int kRollGroupCtrs = 4;   // per group: reads done, dynamics done, reset done, slot-0 stores done
+__host__ __device__ __forceinline__ int roll_group_of_wave(int wave) { return wave >> 2; }
+__host__ __device__ __forceinline__ int roll_group_env0(int j) { return 64 * j; }
+__host__ __device__ __forceinline__ int roll_group_word0(int j) { return 8 * j; }
+__host__ __device__ __forceinline__ int roll_group_dyn_wave(int j) { return 4 * j + j; }
 __host__ __device__ __forceinline__ RollChunkLds roll_chunk_lds(int R, int C, int N) {
   auto a16 = [](int x) { return (x + 15) & ~15; };
   RollChunkLds m;
@@ -46,6 +56,7 @@ __host__ __device__ __forceinline__ RollChunkLds roll_chunk_lds(int R, int C, in
   m.ssa = o;   o = a16(o + 2 * 256 * 2);
   m.sdone = o; o = a16(o + 2 * 256);
   m.shx = o;   o = a16(o + N * 32 * 4);   // (exact body: the outgoing actions, 256 B; every block: the step's hand-off words)
+  m.sgrp = o;  o = a16(o + kRollGroups * kRollGroupCtrs * 4);
   m.total = o;
   return m;
 }
