@@ -515,6 +515,11 @@ int mm_agent_mixer_bwd_seq(const mm_qnet_dims* d, const float* P, int64_t oWq, i
 int mm_agent_bwd_seq(const mm_qnet_dims* d, const float* P, int64_t oWq, int64_t oWhh, int32_t B, const float* save,
                      const int32_t* acts, const float* dqa, const float* done, const float* ones, float* dh,
                      float* dgi, float* dgh, float* dq, int32_t steps, mm_stream_t s);
+/* Steps per LDS window of the serial chunk-sequence kernels at `steps` chunk steps, as the launches compute them:
+ * out[0] the agent BPTT (mm_agent_bwd_seq / mm_agent_mixer_bwd_seq), out[1] the mixer recurrence's backward, out[2]
+ * its forward; a window equal to `steps` means a single pass. Hm = 0 (no mixer recurrence): out[1] = out[2] =
+ * steps. Host only (no device call). */
+int mm_lrn_seq_windows(const mm_qnet_dims* d, int32_t Hm, int32_t steps, int32_t out[3]);
 int mm_agent_bwd(const mm_qnet_dims* d, const float* P, int64_t oWq, int64_t oWhh, int32_t B, const float* save,
                  const int32_t* acts, const float* dqa, const float* done, float* dh, float* dgi, float* dgh,
                  float* dq, mm_stream_t s);

@@ -2994,8 +2994,12 @@ static int mixer_bwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t
     return MM_OK;
   }
   MM_REQUIRE(part == 0, "mixer_bwd_seq: split path not taken");
+  // both fallback kernels keep dhm0 [Hm] in the hypernet deltas' scratch [N*K1 + 3*K1]
+  MM_REQUIRE(Hm <= N * K1 + 3 * K1, "mixer_bwd_seq: Hm = %d above N*K1 + 3*K1 = %d is not supported", Hm,
+             N * K1 + 3 * K1);
   const mm::MixSeqGeo g(Hm, K1, N);
-  if (g.bwd_floats() * 4 <= mm::kMixSeqLds && g.step_in() <= 1024) {
+  // (stage_mixer_image copies one column per lane: Hm <= 64)
+  if (Hm <= 64 && g.bwd_floats() * 4 <= mm::kMixSeqLds && g.step_in() <= 1024) {
     const int rc = mm::mix_seq_lds_setup();
     if (rc) return rc;
     hipLaunchKernelGGL(mm::mixer_bwd_seq_lds_kernel, dim3(B), dim3(256), g.bwd_floats() * 4, (hipStream_t)s, a, q);
@@ -3129,11 +3133,19 @@ int mm_mixer_seq_split(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, 
 int mm_mixer_bwd(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
                  const float* qa, const float* dq, const float* done, float* dhm, float* dqa, float* delta,
                  mm_stream_t s) {
+  MM_REQUIRE(Hm <= N * K1 + 3 * K1, "mixer_bwd: Hm = %d above N*K1 + 3*K1 = %d is not supported", Hm, N * K1 + 3 * K1);
   mm::MixBwdArgs a = {P, save, qa, dq, done, dhm, dqa, delta, B, N, S, Hm, K1};
   const size_t sm = sizeof(float) * ((size_t)8 * Hm + N * K1 + 3 * K1);
   hipLaunchKernelGGL(mm::mixer_bwd_kernel, dim3(B), dim3(256), sm, (hipStream_t)s, a);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
+}
+
+// steps per LDS window of the agent BPTT kernel (halved until agent_bwd_seq_floats fits)
+static int agent_bwd_seq_win(int H, int A, int steps) {
+  int win = steps;
+  while (win > 1 && mm::agent_bwd_seq_floats(H, A, win) * 4 > mm::kMixSeqLds) win = (win + 1) / 2;
+  return win;
 }
 
 // The agent BPTT's kernel arguments and dynamic LDS size (mm_agent_bwd_seq, mm_agent_mixer_bwd_seq)
@@ -3146,8 +3158,7 @@ static int agent_bwd_seq_prep(const mm_qnet_dims* d, const float* P, int64_t oWq
   MM_REQUIRE((d->h == 32 || d->h == 64) && d->n_actions <= 64, "agent_bwd_seq: needs H in {32, 64} and A <= 64");
   MM_REQUIRE(oWhh % 4 == 0 && (uintptr_t)P % 16 == 0 && (uintptr_t)save % 16 == 0 && (d->f1 + d->g) % 4 == 0,
              "agent_bwd_seq: W_hh / save rows must be 16-byte aligned (16-byte LDS-DMA)");
-  int win = steps;
-  while (win > 1 && mm::agent_bwd_seq_floats(d->h, d->n_actions, win) * 4 > mm::kMixSeqLds) win = (win + 1) / 2;
+  const int win = agent_bwd_seq_win(d->h, d->n_actions, steps);
   *smem = sizeof(float) * mm::agent_bwd_seq_floats(d->h, d->n_actions, win);
   MM_REQUIRE(*smem <= mm::kMixSeqLds, "agent_bwd_seq: W_hh too large for LDS");
   {
@@ -3234,6 +3245,16 @@ int mm_agent_mixer_bwd_seq(const mm_qnet_dims* d, const float* P, int64_t oWq, i
   else MM_PAIR(64, 64);
 #undef MM_PAIR
   MM_HIP_CHECK(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_lrn_seq_windows(const mm_qnet_dims* d, int32_t Hm, int32_t steps, int32_t out[3]) {
+  MM_REQUIRE(d && out && steps >= 1, "lrn_seq_windows: bad args");
+  MM_REQUIRE((d->h == 32 || d->h == 64) && d->n_actions <= 64, "lrn_seq_windows: needs H in {32, 64} and A <= 64");
+  MM_REQUIRE(Hm == 0 || mm::mix_rec_supported(Hm), "lrn_seq_windows: Hm must be 0 (no mixer recurrence), 32 or 64");
+  out[0] = agent_bwd_seq_win(d->h, d->n_actions, steps);
+  out[1] = Hm ? mix_rec_win(steps, Hm, true) : steps;
+  out[2] = Hm ? mix_rec_win(steps, Hm, false) : steps;
   return MM_OK;
 }
 

@@ -18,7 +18,7 @@ clip_grad_norm_ on the agent net and on the mixer separately, uniform chunk repl
 (``sample_uniform_and_grads``); its nets are QNet(D->128->32, GRUCell 32) and MixNet(hx 64).
 
 Parameters live in ONE flat fp32 buffer ``P = [agent theta | mixer phi]`` (grads,
-Adam moments alike), the layout the RCCL gradient all-reduce works on.
+Adam moments alike; phi starts at the next multiple of 4 floats), the layout the RCCL gradient all-reduce works on.
 """
 import ctypes
 import math
@@ -147,21 +147,26 @@ class QLearner:
         self.N, self.D, self.F1, self.G, self.H, self.A = d.N, d.D, d.F1, d.G, d.H, d.A
         self.SD = self.F1 + self.G + 6 * self.H
         # one flat buffer [theta | phi]; the nets become views into it
+        # [theta | pad | phi]: the mixer starts 16-byte aligned whatever the agent count (the split / paired mixer
+        # kernels load its weights 16 bytes at a time, mm_mixer_seq_split; n_agents x n_actions bias floats end theta, so
+        # without the pad only some agent counts took them). The pad floats keep a zero gradient and are never read.
         n_t = d.n_params
         n_m = mixer.n_params if mixer is not None else 0
-        self.n_agent, self.n = n_t, n_t + n_m
+        self.n_theta = n_t
+        self.n_agent = n_t + ((-n_t) % 4 if mixer is not None else 0)     # where phi starts
+        self.n = self.n_agent + n_m
         for net in (behavior, mixer):
             if net is not None and getattr(net, "_owner", None) is not None:
                 raise ValueError("this net's parameters already live in another QLearner's flat buffer; "
                                  "give each learner its own AgentQNet / Mixer (copy_from)")
-        self.P = torch.empty(self.n, device=self.dev)
+        self.P = torch.zeros(self.n, device=self.dev)
         self.P[:n_t].copy_(behavior.flat)
         behavior.flat = self.P[:n_t]
         behavior._owner = self
         behavior.mark_dirty()
         if mixer is not None:
-            self.P[n_t:].copy_(mixer.flat)
-            mixer.flat = self.P[n_t:]
+            self.P[self.n_agent:].copy_(mixer.flat)
+            mixer.flat = self.P[self.n_agent:]
             mixer._owner = self
         self.Gr = torch.zeros(self.n, device=self.dev)
         self.m = torch.zeros(self.n, device=self.dev)
@@ -169,7 +174,7 @@ class QLearner:
         self.step_dev = torch.zeros(1, device=self.dev)
         self.partials = torch.zeros(512, device=self.dev)
         self.norm = torch.zeros(2, device=self.dev)
-        self.n_clip = self.n if (not self.has_mixer or clip_mixer) else n_t
+        self.n_clip = self.n if (not self.has_mixer or clip_mixer) else self.n_agent
         self._alloc()
         self.updates = 0
 
@@ -879,7 +884,7 @@ class QLearner:
         drop the ownership marks, so another QLearner can take them; returns the Adam state (m, v, step)
         for a successor over the same nets."""
         torch.cuda.synchronize(self.dev)
-        self.beh.flat = self.P[:self.n_agent].clone()
+        self.beh.flat = self.P[:self.n_theta].clone()
         self.beh._owner = None
         self.beh.mark_dirty()
         if self.mix is not None:

@@ -464,11 +464,16 @@ def test_vdn_double_matches_reference_update(golden):
         np.testing.assert_allclose(L.beh.view(key).cpu().numpy()[sel], after[key].numpy()[sel], atol=2e-6)
 
 
-@pytest.mark.parametrize("mode,f1,g,h,hm", [("qmix", 64, 64, 64, 64), ("vdn", 64, 32, 32, 32),
-                                            ("qmix_min", 128, 32, 32, 64)])
-def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm):
+@pytest.mark.parametrize("mode,f1,g,h,hm,case", [
+    pytest.param("qmix", 64, 64, 64, 64, None, id="qmix-64-64-64-64"),
+    pytest.param("vdn", 64, 32, 32, 32, None, id="vdn-64-32-32-32"),
+    pytest.param("qmix_min", 128, 32, 32, 64, None, id="qmix_min-128-32-32-64"),
+    ("qmix", 64, 64, 64, 64, "w13"), ("qmix", 64, 64, 64, 64, "t50_pair")])
+def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm, case):
     """REC / mixer fwd / mixer bwd / agent bwd as one launch each for all C steps: bit-identical to
-    the per-step launches."""
+    the per-step launches. case: the batch and shape of that case of tests/learner_cases.py instead (w13: the agent
+    BPTT runs two LDS windows, 7 + 6 steps, with dones on both sides of the boundary; t50_pair: B = 50, C = 7, tail
+    blocks in every sequence launch), which pins a window or tail fault to the sequence kernel that has it."""
     from minimarl.learner import Mixer, QLearner
     from minimarl.qnet import AgentQNet
     N, D, A, B, C = 4, 47, 5, 32, 10
@@ -478,6 +483,12 @@ def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm):
     rew = torch.randn(B, C, N, generator=gen)
     dn = (torch.rand(B, C, 1, generator=gen) < 0.25).float()
     w = torch.rand(B, 1, generator=gen) + 0.5
+    if case:
+        from learner_cases import build_case
+        c = build_case(case)
+        assert c.agent == (f1, g, h) and c.mixer == (hm, 32) and c.mode == mode
+        N, D, A, B, C = c.N, c.D, c.A, c.B, c.C
+        st, act, rew, ns, dn, w = c.batch
     out = []
     for seq in (True, False):
         beh = AgentQNet(N, D, A, f1, g, h, DEV, seed=1)
@@ -533,15 +544,16 @@ def test_outer_reduce_batch_large_rows(M, fn):
                                    atol=1e-3 * float(U[k].abs().max()) * np.sqrt(M / 320))
 
 
-@pytest.mark.parametrize("knob", ["mixer", "agent_bwd"])
-def test_multi_sample_blocks_bit_identical(knob):
+@pytest.mark.parametrize("knob,B", [pytest.param("mixer", 600, id="mixer"), pytest.param("agent_bwd", 600, id="agent_bwd"),
+                                    ("mixer", 515), ("agent_bwd", 515)])
+def test_multi_sample_blocks_bit_identical(knob, B):
     """B >= 512 runs the mixer forward with 8 samples per block and the agent backward with 8
     samples per wave (shared weight reads); each must give exactly the one-sample kernel's results
-    (mm_learner_set_multi_sample with that kernel's flag 0)."""
+    (mm_learner_set_multi_sample with that kernel's flag 0). B = 515: a last block / wave of 3 samples."""
     from minimarl._lib import lib
     from minimarl.learner import Mixer, QLearner
     from minimarl.qnet import AgentQNet
-    N, D, A, B, C = 4, 47, 5, 600, 4
+    N, D, A, C = 4, 47, 5, 4
     res = []
     for multi in (1, 0):
         lib().mm_learner_set_multi_sample(multi if knob == "mixer" else 1, multi if knob == "agent_bwd" else 1)
