@@ -414,18 +414,18 @@ int mm_mixer_gi_f16(int32_t R, int32_t N, int32_t S, int32_t Hm, int32_t K1, con
  * ws: [C][B][4][Hm] floats of workspace (B < 512: the hypernet input gradients of every step are
  * computed for all rows at once, then one block per sample runs the serial GRU chain); may be NULL
  * (then the single-launch LDS kernel runs). */
-/* All C steps of the mixer forward for both nets (B < 512): a serial launch with block = (sample, net),
- * the net's W_hh staged once into LDS and the mixer hidden carried in LDS, then the hypernets. Step t's arrays
- * are at the step-0 pointers of nets[] + t * (B x width): gi [B][3Hm] (required, mm_mixer_gi), q [B][N],
- * qtot [B], save [B][mm_mixer_save_dim]; h_out [C][B][Hm] receives the hidden sequence (required: the
- * serial GRU kernel writes it, then one launch runs the hypernets of all C*B rows); step 0 starts
- * from nets[].h_in / reset, step t >= 1 resets where reset_steps[(t-1)*B + b]. Results are
+/* All C steps of the mixer forward for both nets (B < 512, Hm in {32, 64}) as two launches: the GRU recurrence
+ * with block = (sample, net) (W_hh and a window of the steps' gi in LDS; it needs no agent Q), then the hypernets
+ * and the mixing of all C*B rows at once. Step t's arrays are at the step-0 pointers of nets[] + t * (B x width):
+ * gi [B][3Hm] (required, 16-byte aligned, mm_mixer_gi), q [B][N], qtot [B], save [B][mm_mixer_save_dim];
+ * h_out [C][B][Hm] receives the hidden sequence (required: the recurrence writes it, the hypernet launch reads
+ * it); step 0 starts from nets[].h_in / reset, step t >= 1 resets where reset_steps[(t-1)*B + b]. Results are
  * bit-identical to C per-step mm_mixer_fwd launches. mm_mixer_fwd_seq_fits tells whether it applies. */
 int mm_mixer_fwd_seq_fits(int32_t B, int32_t N, int32_t Hm, int32_t K1);
 int mm_mixer_fwd_seq(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const mm_mix_net* nets,
                      int32_t n_nets, int32_t steps, const uint8_t* reset_steps, mm_stream_t s);
-/* The split halves of mm_mixer_fwd_seq / mm_mixer_bwd_seq (same arguments), so the mixer's own recurrence can
- * run on a second stream beside the agent chain (Train_dqn.train, qmix/_train.py:55-116: the Mix_Net GRU over
+/* The two launches of mm_mixer_fwd_seq and of the split mm_mixer_bwd_seq one by one (same arguments), so the mixer's
+ * own recurrence can run beside the agent chain (Train_dqn.train, qmix/_train.py:55-116: the Mix_Net GRU over
  * the state needs no agent Q; its backward needs only the hypernet pass's dhm): fwd_seq_rec -> [join with the
  * agent forward] -> fwd_seq_hyper; bwd_seq_hyper -> {bwd_seq_rec || agent BPTT}. Only where
  * mm_mixer_seq_split(B, N, S, Hm, K1, P, ws, steps) != 0 (else MM_EINVAL). */
@@ -481,9 +481,6 @@ int mm_lrn_loss_ex(int32_t B, int32_t C, int32_t N, float gamma, const float* re
                    const float* isw, const float* qtot, const float* qtot_t, int32_t flags, const float* qa,
                    const float* maxq, float* dq, float* dqa, float* loss_parts, float* td_last, float* loss,
                    mm_stream_t s);
-int mm_lrn_loss(int32_t B, int32_t C, int32_t N, float gamma, const float* rew, const float* done, const float* isw,
-                const float* qtot, const float* qtot_t, int32_t mix_sum, const float* qa, const float* maxq,
-                float* dq, float* dqa, float* loss_parts, float* td_last, float* loss, mm_stream_t s);
 int mm_mixer_bwd(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
                  const float* qa, const float* dq, const float* done, float* dhm, float* dqa, float* delta,
                  mm_stream_t s);
@@ -531,7 +528,6 @@ typedef struct mm_outer_args {
   float* db; int64_t b_g;
   int32_t M, R, Cc, accumulate, groups;
 } mm_outer_args;
-int mm_outer_reduce(const mm_outer_args* x, mm_stream_t s);
 /* Up to 16 independent outer-reduce jobs in one launch (M split into 32-row slices, partials summed
  * in fixed order by a second launch: deterministic). partial: device floats, size from
  * mm_outer_reduce_batch_partial(jobs, n). */

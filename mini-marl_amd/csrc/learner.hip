@@ -620,11 +620,11 @@ __global__ __launch_bounds__(256) void mixer_fwd_multi_kernel(MixFwdArgs a) {
 }
 
 // ------------------------------------------------------------------ mixer sequences with LDS-resident weights
-// Small batches (B < 512): one block per (sample, net) runs ALL C steps of the mixer forward (or
-// backward) in one launch, with the net's W_hh and hypernet weights staged ONCE into LDS (row
-// stride Hm + 1: conflict-free for both the row-per-lane forward and the column-per-lane transposed
-// backward) and the recurrent state carried in LDS between steps. Per-step arithmetic and summation
-// order are exactly mixer_fwd_body / mixer_bwd_body's (bit-identical to the per-step launches).
+// Small batches (B < 512) outside the split path: one block per sample runs ALL C steps of the mixer
+// backward in one launch (mixer_bwd_seq_lds_kernel), with the net's W_hh and hypernet weights staged
+// ONCE into LDS (row stride Hm + 1: conflict-free for the column-per-lane transposed reads) and the
+// recurrent state carried in LDS between steps. Per-step arithmetic and summation order are exactly
+// mixer_bwd_body's (bit-identical to the per-step launches).
 // Image rows: [W_hh (3Hm) | w1W (N*K1) | b1W (K1) | w2W (K1) | b2aW (K1)] = the forward's hypernet
 // row order after W_hh.
 struct MixSeqGeo {
@@ -634,8 +634,6 @@ struct MixSeqGeo {
   __host__ __device__ size_t img() const { return (size_t)rows * ld; }
   // biases staged with the image: b_hh [3Hm] | hypernet biases [RW] | b2 output weights [K1] + bias [1]
   __host__ __device__ size_t bias() const { return (size_t)3 * Hm + RW + K1 + 1; }
-  // forward scratch: h0, gi, gh, h1, hyp, yp, q (N), reset flag
-  __host__ __device__ size_t fwd_floats() const { return img() + bias() + 8 * Hm + RW + K1 + N + 4; }
   // backward scratch: dhm, dhm1, dgh, shd, red, 2 x prefetched step inputs (save row + qa + dq + done)
   __host__ __device__ size_t step_in() const { return (size_t)mix_save_dim(Hm, K1, N) + N + 2; }
   __host__ __device__ size_t bwd_floats() const { return img() + bias() + 5 * Hm + RW + 4 * Hm + 2 * step_in(); }
@@ -683,118 +681,6 @@ __device__ void stage_mixer_bias(const float* __restrict__ P, const MixOff& o, c
     else v = P[o.b2bb];
     bs[i] = v;
   }
-}
-
-struct MixFwdSeq {
-  int C;
-  int64_t gi_st, q_st, qtot_st, save_st, hout_st;
-  const uint8_t* reset_steps;  // [C-1][B]: reset flags of steps t >= 1 (step 0 uses net.reset / h_in)
-};
-
-__device__ __forceinline__ void mixer_fwd_seq_body(const MixFwdArgs& a, const MixFwdNet& nt, const MixFwdSeq& sq) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int b = blockIdx.x;
-  const int S = a.S, Hm = a.Hm, K1 = a.K1, N = a.N;
-  const MixOff o = mix_offsets(S, Hm, K1, N);
-  const MixSeqGeo g(Hm, K1, N);
-  const int NK = g.NK, RW = g.RW, ld = g.ld, M3 = 3 * Hm;
-  float* img = sm;
-  float* bs = img + g.img();   // biases (stage_mixer_bias)
-  float* h0 = bs + g.bias();   // [Hm]
-  float* gi = h0 + Hm;         // [3Hm] this step's input projection
-  float* gh = gi + 3 * Hm;     // [3Hm]
-  float* h1 = gh + 3 * Hm;     // [Hm]
-  float* hyp = h1 + Hm;        // [RW]
-  float* yp = hyp + RW;        // [K1]
-  float* qs = yp + K1;         // [N] this step's agent values
-  float* rst = qs + N;         // [1] reset flag of the next step
-  stage_mixer_image(nt.P, o, g, img);
-  stage_mixer_bias(nt.P, o, g, bs);
-  const float* b_hh = bs;
-  const float* b_hy = bs + M3;
-  const float* b2w = bs + M3 + RW;
-  const int svd = mix_save_dim(Hm, K1, N);
-  {
-    const bool rz = !nt.h_in || (nt.reset && nt.reset[b]);
-    for (int i = threadIdx.x; i < Hm; i += blockDim.x) h0[i] = rz ? 0.f : nt.h_in[(int64_t)b * Hm + i];
-    for (int i = threadIdx.x; i < M3; i += blockDim.x) gi[i] = nt.gi[(int64_t)b * M3 + i];
-    for (int i = threadIdx.x; i < N; i += blockDim.x) qs[i] = nt.q[(int64_t)b * N + i];
-  }
-  __syncthreads();
-  for (int t = 0; t < sq.C; ++t) {
-    // prefetch step t+1's inputs into registers (written to LDS after their last use in step t)
-    const bool more = t + 1 < sq.C;
-    const int ti = (int)threadIdx.x;
-    const float g_nx = (more && ti < M3) ? nt.gi[(t + 1) * sq.gi_st + (int64_t)b * M3 + ti] : 0.f;
-    const float q_nx = (more && ti < N) ? nt.q[(t + 1) * sq.q_st + (int64_t)b * N + ti] : 0.f;
-    const float r_nx = (more && ti == 0) ? (sq.reset_steps[(int64_t)t * a.B + b] != 0 ? 1.f : 0.f) : 0.f;
-    // gh = W_hh h0 + b_hh (block_matvec order: sequential k, bias last)
-    for (int r = threadIdx.x; r < M3; r += blockDim.x) gh[r] = dot_seq_n(img + r * ld, h0, Hm, 0.f) + b_hh[r];
-    lds_sync();
-    float* sv = nt.save ? nt.save + t * sq.save_st + (int64_t)b * svd : nullptr;
-    float* hout = nt.h_out ? nt.h_out + t * sq.hout_st : nullptr;
-    for (int i = threadIdx.x; i < Hm; i += blockDim.x) {
-      const float r = sigmoidf_(gi[i] + gh[i]);
-      const float z = sigmoidf_(gi[Hm + i] + gh[Hm + i]);
-      const float n = tanhf_(gi[2 * Hm + i] + r * gh[2 * Hm + i]);
-      const float hv = n + z * (h0[i] - n);
-      h1[i] = hv;
-      if (hout) hout[(int64_t)b * Hm + i] = hv;
-      if (sv) {
-        sv[i] = h0[i];
-        sv[Hm + i] = r;
-        sv[2 * Hm + i] = z;
-        sv[3 * Hm + i] = n;
-        sv[4 * Hm + i] = gh[2 * Hm + i];
-        sv[5 * Hm + i] = hv;
-      }
-    }
-    lds_sync();
-    // hypernets on h1 (rows w1 [NK] | b1 [K1] | w2 [K1] | b2 hidden [K1]), each row's bias last
-    for (int r = threadIdx.x; r < RW; r += blockDim.x) hyp[r] = dot_seq_n(img + (M3 + r) * ld, h1, Hm, 0.f) + b_hy[r];
-    lds_sync();
-    for (int k = threadIdx.x; k < K1; k += blockDim.x) {
-      float acc = 0.f;
-      for (int i = 0; i < N; ++i) acc += fabsf(hyp[k * N + i]) * qs[i];
-      yp[k] = acc + hyp[NK + k];
-    }
-    lds_sync();
-    if (threadIdx.x == 0) {
-      const float* w2raw = hyp + NK + K1;
-      const float* b2pre = hyp + NK + 2 * K1;
-      float b2 = 0.f;
-      for (int k = 0; k < K1; ++k) b2 += b2w[k] * fmaxf(b2pre[k], 0.f);
-      b2 += b2w[K1];
-      float acc = 0.f;
-      for (int k = 0; k < K1; ++k) acc += fabsf(w2raw[k]) * fmaxf(yp[k], 0.f);
-      nt.qtot[t * sq.qtot_st + b] = acc + b2;
-      if (sv) sv[6 * Hm + NK + 4 * K1] = b2;
-    }
-    if (sv) {
-      for (int i = threadIdx.x; i < RW; i += blockDim.x) sv[6 * Hm + i] = i >= NK + 2 * K1 ? fmaxf(hyp[i], 0.f) : hyp[i];
-      for (int k = threadIdx.x; k < K1; k += blockDim.x) sv[6 * Hm + NK + 3 * K1 + k] = yp[k];
-    }
-    // next step's inputs (gi / q were last read above); h0 <- h1 unless the next step resets
-    if (more) {
-      if (ti < M3) gi[ti] = g_nx;
-      if (ti < N) qs[ti] = q_nx;
-      if (ti == 0) rst[0] = r_nx;
-    }
-    lds_sync();
-    if (more) {
-      const bool rz = rst[0] != 0.f;
-      for (int i = threadIdx.x; i < Hm; i += blockDim.x) h0[i] = rz ? 0.f : h1[i];
-    }
-    lds_sync();
-  }
-}
-
-// one inlined body per net: each reads its own kernel-argument fields with scalar loads
-__global__ __launch_bounds__(256) void mixer_fwd_seq_lds_kernel(MixFwdArgs a, MixFwdSeq sq) {
-  if (blockIdx.y == 0)
-    mixer_fwd_seq_body(a, a.net[0], sq);
-  else
-    mixer_fwd_seq_body(a, a.net[1], sq);
 }
 
 // ------------------------------------------------------------------ loss (all steps at once)
@@ -1825,22 +1711,88 @@ __global__ __launch_bounds__(256) void mixer_rec_bwd_kernel(MixBwdArgs a, MixRec
 // dynamic-LDS limit of the sequence kernels (MI355X: 160 KB per CU, one block per CU)
 constexpr size_t kMixSeqLds = 160 * 1024;
 static int mix_seq_lds_setup() {
-  static bool done = false;
-  if (done) return MM_OK;
-  MM_HIP_CHECK(hipFuncSetAttribute((const void*)mixer_fwd_seq_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kMixSeqLds));
-  MM_HIP_CHECK(hipFuncSetAttribute((const void*)mixer_bwd_seq_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kMixSeqLds));
-  const void* serial[] = {(const void*)mixer_rec_fwd_kernel<32>, (const void*)mixer_rec_fwd_kernel<64>,
-                          (const void*)mixer_rec_bwd_kernel<32>, (const void*)mixer_rec_bwd_kernel<64>,
-                          (const void*)mixer_hyper_bwd_kernel<false>};
-  for (const void* k : serial)
-    MM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMixSeqLds));
-  // (the PER block's static LDS comes off the dynamic limit)
-  MM_HIP_CHECK(hipFuncSetAttribute((const void*)mixer_hyper_bwd_kernel<true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMixSeqLds - kPerSmallLds)));
-  done = true;
-  return MM_OK;
+  // thread-safe one-time setup (a function-local static's initialiser runs once)
+  static const int attr_rc = []() -> int {
+    const void* k[] = {(const void*)mixer_bwd_seq_lds_kernel,     (const void*)mixer_rec_fwd_kernel<32>,
+                       (const void*)mixer_rec_fwd_kernel<64>,     (const void*)mixer_rec_bwd_kernel<32>,
+                       (const void*)mixer_rec_bwd_kernel<64>,     (const void*)mixer_hyper_bwd_kernel<false>};
+    for (const void* f : k)
+      MM_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMixSeqLds));
+    // (the PER block's static LDS comes off the dynamic limit)
+    MM_HIP_CHECK(hipFuncSetAttribute((const void*)mixer_hyper_bwd_kernel<true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMixSeqLds - kPerSmallLds)));
+    return MM_OK;
+  }();
+  return attr_rc;
+}
+
+// steps per LDS window of the serial mixer kernels
+static int mix_rec_win(int C, int Hm, bool bwd) {
+  int win = C;
+  while (win > 1 && (bwd ? mix_rec_bwd_floats(Hm, win) : mix_rec_fwd_floats(Hm, win)) * 4 > kMixSeqLds)
+    win = (win + 1) / 2;
+  return win;
+}
+
+// ---- one builder per kernel-argument struct of the mixer launches (the separate and the paired launches alike)
+static MixGiArgs mix_gi_args(int R, int N, int S, int Hm, int K1, const float* obs, const float* reset_obs,
+                             const float* P0, const int64_t* s_off0, float* gi0, const float* P1,
+                             const int64_t* s_off1, float* gi1) {
+  MixGiArgs a;
+  a.net[0] = {P0, s_off0, gi0};
+  a.net[1] = {P1 ? P1 : P0, P1 ? s_off1 : s_off0, P1 ? gi1 : gi0};   // one net: the second slot repeats it
+  a.obs = obs;
+  a.reset_obs = reset_obs;
+  a.R = R;
+  a.S = S;
+  a.Hm = Hm;
+  a.K1 = K1;
+  a.N = N;
+  return a;
+}
+
+static MixFwdArgs mix_fwd_args(const mm_mix_net* nets, int n_nets, int B, int N, int S, int Hm, int K1,
+                               const float* obs, const float* reset_obs) {
+  MixFwdArgs a;
+  for (int i = 0; i < 2; ++i) {
+    const mm_mix_net& n = nets[i < n_nets ? i : 0];
+    a.net[i] = {n.P, n.gi, n.q, n.s_off, n.h_in, n.reset, n.h_out, n.qtot, n.save};
+  }
+  a.obs = obs;
+  a.reset_obs = reset_obs;
+  a.B = B;
+  a.N = N;
+  a.S = S;
+  a.Hm = Hm;
+  a.K1 = K1;
+  return a;
+}
+
+static MixRecFwd mix_rec_fwd_args(int B, int N, int Hm, int K1, int steps, const uint8_t* reset_steps) {
+  MixRecFwd q;
+  q.C = steps;
+  q.win = mix_rec_win(steps, Hm, false);
+  q.gi_st = (int64_t)B * 3 * Hm;
+  q.hout_st = (int64_t)B * Hm;
+  q.save_st = (int64_t)B * mix_save_dim(Hm, K1, N);
+  q.reset_steps = reset_steps;
+  q.trace = debug_trace_buffer("MM_MIX_TRACE_FWD");
+  return q;
+}
+
+static MixRecBwd mix_rec_bwd_args(int B, int N, int Hm, int K1, int steps, const float* done, const float* ws,
+                                  const float* ones) {
+  MixRecBwd q;
+  q.C = steps;
+  q.win = mix_rec_win(steps, Hm, true);
+  q.save_st = (int64_t)B * mix_save_dim(Hm, K1, N);
+  q.delta_st = (int64_t)B * mix_delta_dim(Hm, K1, N);
+  q.done_st = B;
+  q.done = done;
+  q.xws = ws;
+  q.ones = ones;
+  q.trace = debug_trace_buffer("MM_MIX_TRACE_BWD");
+  return q;
 }
 // ------------------------------------------------------------------ agent backward chain (one step)
 struct AgentBwdArgs {
@@ -2164,80 +2116,6 @@ struct OuterArgs {
   float* db; int64_t b_g;   // db[g*b_g + r] (nullptr: none)
   int M, R, Cc, accumulate;
 };
-
-__global__ __launch_bounds__(256) void outer_reduce_kernel(OuterArgs a) {
-  // LDS double buffer + register prefetch: chunk m0+32 is loaded while chunk m0 is reduced, so
-  // the M/32 sequential steps pay one memory latency instead of one each.
-  __shared__ float su[2][32][33];
-  __shared__ float svv[2][32][33];
-  const int g = blockIdx.z;
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-  const int tr = threadIdx.x / 32, tc = threadIdx.x % 32;  // tr in [0,8): rows tr, tr+8, tr+16, tr+24
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float accb = 0.f;
-  float pu[4], pv[4];
-  auto fetch = [&](int m0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = threadIdx.x + 256 * q;
-      const int mm = k / 32, x = k % 32;
-      const int m = m0 + mm;
-      float u = 0.f, v = 0.f;
-      if (m < a.M) {
-        if (r0 + x < a.R) u = a.U[g * a.u_g + (int64_t)m * a.u_m + r0 + x];
-        if (c0 + x < a.Cc) {
-          if (a.v_off) {
-            const int64_t off = a.v_off[m];
-            const float* base = off >= 0 ? a.V + off : a.v_reset;
-            v = base[g * a.v_g + c0 + x];
-          } else {
-            v = a.V[g * a.v_g + (int64_t)m * a.v_m + c0 + x];
-          }
-        }
-      }
-      pu[q] = u;
-      pv[q] = v;
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = threadIdx.x + 256 * q;
-      su[buf][k / 32][k % 32] = pu[q];
-      svv[buf][k / 32][k % 32] = pv[q];
-    }
-  };
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  int buf = 0;
-  for (int m0 = 0; m0 < a.M; m0 += 32) {
-    const bool more = m0 + 32 < a.M;
-    if (more) fetch(m0 + 32);
-    for (int mm = 0; mm < 32; ++mm) {
-      const float v = svv[buf][mm][tc];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] += su[buf][mm][tr + 8 * q] * v;
-    }
-    if (a.db && blockIdx.x == 0 && threadIdx.x < 32)
-      for (int mm = 0; mm < 32; ++mm) accb += su[buf][mm][threadIdx.x];
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = r0 + tr + 8 * q, c = c0 + tc;
-    if (r < a.R && c < a.Cc) {
-      float* o = a.dW + g * a.w_g + (int64_t)r * a.Cc + c;
-      *o = a.accumulate ? *o + acc[q] : acc[q];
-    }
-  }
-  if (a.db && blockIdx.x == 0 && threadIdx.x < 32 && r0 + threadIdx.x < a.R) {
-    float* o = a.db + g * a.b_g + r0 + threadIdx.x;
-    *o = a.accumulate ? *o + accb : accb;
-  }
-}
 
 // Batched split-M outer reduce: many independent OuterArgs jobs in ONE launch, each job's M rows
 // split into slices of 32-row chunks; block (job, tile, group, slice) reduces one tile over one slice
@@ -2791,18 +2669,7 @@ int mm_mixer_fwd(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const 
                  const mm_mix_net* nets, int32_t n_nets, mm_stream_t s) {
   MM_REQUIRE(nets && n_nets >= 1 && n_nets <= 2 && B > 0, "mixer_fwd: bad args");
   MM_REQUIRE(3 * Hm <= 4096 && N * K1 <= 4096, "mixer_fwd: dims too large");
-  mm::MixFwdArgs a;
-  for (int i = 0; i < 2; ++i) {
-    const mm_mix_net& n = nets[i < n_nets ? i : 0];
-    a.net[i] = {n.P, n.gi, n.q, n.s_off, n.h_in, n.reset, n.h_out, n.qtot, n.save};
-  }
-  a.obs = obs;
-  a.reset_obs = reset_obs;
-  a.B = B;
-  a.N = N;
-  a.S = S;
-  a.Hm = Hm;
-  a.K1 = K1;
+  const mm::MixFwdArgs a = mm::mix_fwd_args(nets, n_nets, B, N, S, Hm, K1, obs, reset_obs);
   const size_t sm = sizeof(float) * ((size_t)S + 9 * Hm + N * K1 + 4 * K1);
   MM_REQUIRE(sm <= 64 * 1024, "mixer_fwd: state too large for LDS (%zu B)", sm);
   bool all_gi = true;
@@ -2823,16 +2690,7 @@ int mm_mixer_gi(int32_t R, int32_t N, int32_t S, int32_t Hm, int32_t K1, const f
                 const float* P0, const int64_t* s_off0, float* gi0, const float* P1, const int64_t* s_off1, float* gi1,
                 mm_stream_t s) {
   MM_REQUIRE(R > 0 && P0 && gi0 && obs && (s_off0 || !P1), "mixer_gi: bad args");
-  mm::MixGiArgs a;
-  a.net[0] = {P0, s_off0, gi0};
-  a.net[1] = {P1 ? P1 : P0, P1 ? s_off1 : s_off0, P1 ? gi1 : gi0};
-  a.obs = obs;
-  a.reset_obs = reset_obs;
-  a.R = R;
-  a.S = S;
-  a.Hm = Hm;
-  a.K1 = K1;
-  a.N = N;
+  const mm::MixGiArgs a = mm::mix_gi_args(R, N, S, Hm, K1, obs, reset_obs, P0, s_off0, gi0, P1, s_off1, gi1);
   // small R (B = 32 updates): the split-K register kernel gives more blocks and wins
   if (R >= 2048) {
     dim3 grid((3 * Hm + 63) / 64, (R + 63) / 64, P1 ? 2 : 1);
@@ -2852,16 +2710,7 @@ int mm_mixer_gi_f16(int32_t R, int32_t N, int32_t S, int32_t Hm, int32_t K1, con
   MM_REQUIRE(R > 0 && P0 && gi0 && obs && (s_off0 || !P1), "mixer_gi_f16: bad args");
   MM_REQUIRE(Hm == 32 || Hm == 64, "mixer_gi_f16: Hm must be 32 or 64");
   MM_REQUIRE((((uintptr_t)gi0 | (uintptr_t)gi1) & 15) == 0, "mixer_gi_f16: gi must be 16-byte aligned");
-  mm::MixGiArgs a;
-  a.net[0] = {P0, s_off0, gi0};
-  a.net[1] = {P1 ? P1 : P0, P1 ? s_off1 : s_off0, P1 ? gi1 : gi0};
-  a.obs = obs;
-  a.reset_obs = reset_obs;
-  a.R = R;
-  a.S = S;
-  a.Hm = Hm;
-  a.K1 = K1;
-  a.N = N;
+  const mm::MixGiArgs a = mm::mix_gi_args(R, N, S, Hm, K1, obs, reset_obs, P0, s_off0, gi0, P1, s_off1, gi1);
   dim3 grid((R + 63) / 64, P1 ? 2 : 1);
   if (Hm == 32)
     hipLaunchKernelGGL(mm::mixer_gi_f16_kernel<3>, grid, dim3(384), 0, (hipStream_t)s, a);
@@ -2894,47 +2743,32 @@ int mm_lrn_loss_ex(int32_t B, int32_t C, int32_t N, float gamma, const float* re
   return MM_OK;
 }
 
-int mm_lrn_loss(int32_t B, int32_t C, int32_t N, float gamma, const float* rew, const float* done, const float* isw,
-                const float* qtot, const float* qtot_t, int32_t mix_sum, const float* qa, const float* maxq,
-                float* dq, float* dqa, float* loss_parts, float* td_last, float* loss, mm_stream_t s) {
-  const int n = B * C;
-  hipLaunchKernelGGL(mm::lrn_loss_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, B, C, N, gamma, rew,
-                     done, isw, qtot, qtot_t, mix_sum ? MM_LOSS_MIX_SUM : 0, qa, maxq, dq, dqa, loss_parts, td_last);
-  MM_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(mm::lrn_loss_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, B, C, loss_parts, loss);
-  MM_HIP_CHECK(hipGetLastError());
-  return MM_OK;
+// the shapes and alignments the split (hypernet + recurrence) mixer backward kernels take, at any batch size
+static bool mix_bwd_split_fits(int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* ws,
+                               int32_t steps) {
+  const int win = mm::mix_rec_win(steps, Hm, true);
+  return ws && mm::mix_rec_supported(Hm) && mm::mix_rec_bwd_floats(Hm, win) * 4 <= mm::kMixSeqLds &&
+         mm::mix_hyper_bwd_floats(Hm, K1, N) * 4 <= mm::kMixSeqLds && Hm % 4 == 0 && K1 % 4 == 0 &&
+         mm::mix_offsets(S, Hm, K1, N).w1W % 4 == 0 && (uintptr_t)P % 16 == 0 && (uintptr_t)ws % 16 == 0;
 }
 
-static bool mix_split_enabled() { return true; }   // split recurrence / hypernet launches (the LDS sequence kernels
-                                                    // remain the fallback for shapes the split path does not take)
-// steps per LDS window of the serial mixer kernels
-static int mix_rec_win(int C, int Hm, bool bwd) {
-  int win = C;
-  while (win > 1 && (bwd ? mm::mix_rec_bwd_floats(Hm, win) : mm::mix_rec_fwd_floats(Hm, win)) * 4 > mm::kMixSeqLds)
-    win = (win + 1) / 2;
-  return win;
-}
-
-// the split (hypernet + recurrence) mixer backward applies: one launch each, so a caller may run the recurrence
-// beside the agent BPTT (it reads only the mixer's own saves and the hypernet pass's dhm / delta)
+// the split mixer backward applies: one launch each, so a caller may run the recurrence beside the agent BPTT (it
+// reads only the mixer's own saves and the hypernet pass's dhm / delta)
 static bool mix_bwd_split_ok(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* ws,
                              int32_t steps) {
-  const int win = mix_rec_win(steps, Hm, true);
-  return B < 512 && ws && mix_split_enabled() && mm::mix_rec_supported(Hm) &&
-         mm::mix_rec_bwd_floats(Hm, win) * 4 <= mm::kMixSeqLds && mm::mix_hyper_bwd_floats(Hm, K1, N) * 4 <= mm::kMixSeqLds &&
-         Hm % 4 == 0 && K1 % 4 == 0 && mm::mix_offsets(S, Hm, K1, N).w1W % 4 == 0 && (uintptr_t)P % 16 == 0 &&
-         (uintptr_t)ws % 16 == 0;
+  return B < 512 && mix_bwd_split_fits(N, S, Hm, K1, P, ws, steps);
 }
 
-// part 0: the whole backward; 1: the hypernet pass only (dq -> dqa, dhm, delta); 2: the recurrence only
-// pu (part 1, may be null): the PER priority update as one more block of the hypernet launch
-static int mixer_bwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P,
+// Hyper: the hypernet pass only (dq -> dqa, dhm, delta); Rec: the recurrence only
+enum class MixSeqPart { All, Rec, Hyper };
+
+// pu (Hyper, may be null): the PER priority update as one more block of the hypernet launch
+static int mixer_bwd_seq_part(MixSeqPart part, int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P,
                               const float* save, const float* qa, const float* dq, const float* done, const float* ones,
                               float* dhm, float* dqa, float* delta, float* ws, int32_t steps, mm_stream_t s,
                               const mm::PerUpd* pu = nullptr) {
   MM_REQUIRE(P && save && qa && dq && done && ones && dhm && dqa && delta && steps >= 1, "mixer_bwd_seq: bad args");
-  MM_REQUIRE(part == 0 || mix_bwd_split_ok(B, N, S, Hm, K1, P, ws, steps),
+  MM_REQUIRE(part == MixSeqPart::All || mix_bwd_split_ok(B, N, S, Hm, K1, P, ws, steps),
              "mixer_bwd_seq: the hypernet / recurrence parts need the split path (mm_mixer_seq_split)");
   mm::MixBwdArgs a = {P, save, qa, dq, done, dhm, dqa, delta, B, N, S, Hm, K1};
   mm::MixBwdSeq q;
@@ -2953,15 +2787,12 @@ static int mixer_bwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
   }
-  const int win = mix_rec_win(steps, Hm, true);
   MM_REQUIRE(!ws || (uintptr_t)ws % 16 == 0, "mixer_bwd_seq: ws must be 16-byte aligned");
-  if (ws && mix_split_enabled() && mm::mix_rec_supported(Hm) && mm::mix_rec_bwd_floats(Hm, win) * 4 <= mm::kMixSeqLds &&
-      mm::mix_hyper_bwd_floats(Hm, K1, N) * 4 <= mm::kMixSeqLds && Hm % 4 == 0 && K1 % 4 == 0 &&
-      mm::mix_offsets(S, Hm, K1, N).w1W % 4 == 0 && (uintptr_t)P % 16 == 0) {
+  if (mix_bwd_split_fits(N, S, Hm, K1, P, ws, steps)) {
     const int rc = mm::mix_seq_lds_setup();
     if (rc) return rc;
     const int R = B * steps;
-    if (part != 2) {
+    if (part != MixSeqPart::Rec) {
       const int nbh = (R + mm::MIX_SPB - 1) / mm::MIX_SPB;
       if (pu)
         hipLaunchKernelGGL(mm::mixer_hyper_bwd_kernel<true>, dim3(nbh + 1), dim3(256),
@@ -2973,27 +2804,18 @@ static int mixer_bwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t
                            mm::debug_trace_buffer("MM_HYB_TRACE"), mm::PerUpd{});
       MM_HIP_CHECK(hipGetLastError());
     }
-    if (part == 1) return MM_OK;
-    mm::MixRecBwd rq;
-    rq.C = steps;
-    rq.win = win;
-    rq.save_st = q.save_st;
-    rq.delta_st = q.delta_st;
-    rq.done_st = B;
-    rq.done = done;
-    rq.xws = ws;
-    rq.ones = ones;
-    rq.trace = mm::debug_trace_buffer("MM_MIX_TRACE_BWD");
+    if (part == MixSeqPart::Hyper) return MM_OK;
+    const mm::MixRecBwd rq = mm::mix_rec_bwd_args(B, N, Hm, K1, steps, done, ws, ones);
     if (Hm == 32)
-      hipLaunchKernelGGL(mm::mixer_rec_bwd_kernel<32>, dim3(B), dim3(256), mm::mix_rec_bwd_floats(Hm, win) * 4,
+      hipLaunchKernelGGL(mm::mixer_rec_bwd_kernel<32>, dim3(B), dim3(256), mm::mix_rec_bwd_floats(Hm, rq.win) * 4,
                          (hipStream_t)s, a, rq);
     else
-      hipLaunchKernelGGL(mm::mixer_rec_bwd_kernel<64>, dim3(B), dim3(256), mm::mix_rec_bwd_floats(Hm, win) * 4,
+      hipLaunchKernelGGL(mm::mixer_rec_bwd_kernel<64>, dim3(B), dim3(256), mm::mix_rec_bwd_floats(Hm, rq.win) * 4,
                          (hipStream_t)s, a, rq);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
   }
-  MM_REQUIRE(part == 0, "mixer_bwd_seq: split path not taken");
+  MM_REQUIRE(part == MixSeqPart::All, "mixer_bwd_seq: split path not taken");
   // both fallback kernels keep dhm0 [Hm] in the hypernet deltas' scratch [N*K1 + 3*K1]
   MM_REQUIRE(Hm <= N * K1 + 3 * K1, "mixer_bwd_seq: Hm = %d above N*K1 + 3*K1 = %d is not supported", Hm,
              N * K1 + 3 * K1);
@@ -3015,119 +2837,85 @@ static int mixer_bwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t
 int mm_mixer_bwd_seq(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
                      const float* qa, const float* dq, const float* done, const float* ones, float* dhm, float* dqa,
                      float* delta, float* ws, int32_t steps, mm_stream_t s) {
-  return mixer_bwd_seq_part(0, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps, s);
+  return mixer_bwd_seq_part(MixSeqPart::All, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps,
+                            s);
 }
 int mm_mixer_bwd_seq_hyper(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
                            const float* qa, const float* dq, const float* done, const float* ones, float* dhm,
                            float* dqa, float* delta, float* ws, int32_t steps, mm_stream_t s) {
-  return mixer_bwd_seq_part(1, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps, s);
+  return mixer_bwd_seq_part(MixSeqPart::Hyper, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws,
+                            steps, s);
 }
 int mm_mixer_bwd_seq_rec(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
                          const float* qa, const float* dq, const float* done, const float* ones, float* dhm, float* dqa,
                          float* delta, float* ws, int32_t steps, mm_stream_t s) {
-  return mixer_bwd_seq_part(2, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps, s);
+  return mixer_bwd_seq_part(MixSeqPart::Rec, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps,
+                            s);
 }
 
 int mm_mixer_fwd_seq_fits(int32_t B, int32_t N, int32_t Hm, int32_t K1) {
-  const mm::MixSeqGeo g(Hm, K1, N);
-  if (mix_split_enabled())
-    return B < 512 && mm::mix_rec_supported(Hm) && mm::mix_rec_fwd_floats(Hm, 1) * 4 <= mm::kMixSeqLds &&
-           mm::mix_hyper_fwd_floats(Hm, K1, N) * 4 <= 64 * 1024;
-  return B < 512 && g.fwd_floats() * 4 <= mm::kMixSeqLds && 3 * Hm <= 256 && N <= 256;
+  return B < 512 && mm::mix_rec_supported(Hm) && mm::mix_rec_fwd_floats(Hm, 1) * 4 <= mm::kMixSeqLds &&
+         mm::mix_hyper_fwd_floats(Hm, K1, N) * 4 <= 64 * 1024;
 }
 
-// part 0: the whole forward; 1: the mixer recurrence only (reads gi, not the agents' Q: a caller may run it
-// beside the agent forward); 2: the hypernet pass only (after both)
-// part 3: no launch, the recurrence's arguments into *a_out / *rq_out (a paired launch, mm_agent_mixer_rec_seq)
-static int mixer_fwd_seq_part(int part, int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const mm_mix_net* nets,
-                              int32_t n_nets, int32_t steps, const uint8_t* reset_steps, mm_stream_t s,
-                              mm::MixFwdArgs* a_out = nullptr, mm::MixRecFwd* rq_out = nullptr) {
+// what the mixer forward's sequence launches (mixer_fwd_seq_part, the paired mm_agent_mixer_rec_seq) require
+static int mixer_fwd_seq_check(int32_t B, int32_t N, int32_t Hm, int32_t K1, const mm_mix_net* nets, int32_t n_nets,
+                               int32_t steps, const uint8_t* reset_steps) {
   MM_REQUIRE(nets && n_nets >= 1 && n_nets <= 2 && B > 0 && steps >= 1, "mixer_fwd_seq: bad args");
-  MM_REQUIRE(part == 0 || mix_split_enabled(), "mixer_fwd_seq: the parts need the split path");
   MM_REQUIRE(steps == 1 || reset_steps, "mixer_fwd_seq: reset_steps required for steps > 1");
-  MM_REQUIRE(mm_mixer_fwd_seq_fits(B, N, Hm, K1), "mixer_fwd_seq: B >= 512 or the weights exceed the LDS");
-  for (int i = 0; i < n_nets; ++i)
+  MM_REQUIRE(mm_mixer_fwd_seq_fits(B, N, Hm, K1), "mixer_fwd_seq: B >= 512 or the kernels' scratch exceeds the LDS");
+  for (int i = 0; i < n_nets; ++i) {
     MM_REQUIRE(nets[i].gi && nets[i].q && nets[i].qtot, "mixer_fwd_seq: gi / q / qtot required");
-  mm::MixFwdArgs a;
-  for (int i = 0; i < 2; ++i) {
-    const mm_mix_net& n = nets[i < n_nets ? i : 0];
-    a.net[i] = {n.P, n.gi, n.q, n.s_off, n.h_in, n.reset, n.h_out, n.qtot, n.save};
+    MM_REQUIRE(nets[i].h_out, "mixer_fwd_seq: h_out [C][B][Hm] required");
+    MM_REQUIRE((uintptr_t)nets[i].gi % 16 == 0, "mixer_fwd_seq: gi must be 16-byte aligned");
   }
-  a.obs = nullptr;
-  a.reset_obs = nullptr;
-  a.B = B;
-  a.N = N;
-  a.S = S;
-  a.Hm = Hm;
-  a.K1 = K1;
-  mm::MixFwdSeq q;
-  q.C = steps;
-  q.gi_st = (int64_t)B * 3 * Hm;
-  q.q_st = (int64_t)B * N;
-  q.qtot_st = B;
-  q.save_st = (int64_t)B * mm::mix_save_dim(Hm, K1, N);
-  q.hout_st = 0;
-  q.reset_steps = reset_steps;
-  const int rc = mm::mix_seq_lds_setup();
+  return MM_OK;
+}
+
+// Rec: the mixer recurrence only (reads gi, not the agents' Q: a caller may run it beside the agent forward);
+// Hyper: the hypernet pass only (after both)
+static int mixer_fwd_seq_part(MixSeqPart part, int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1,
+                              const mm_mix_net* nets, int32_t n_nets, int32_t steps, const uint8_t* reset_steps,
+                              mm_stream_t s) {
+  int rc = mixer_fwd_seq_check(B, N, Hm, K1, nets, n_nets, steps, reset_steps);
   if (rc) return rc;
-  if (mix_split_enabled()) {
-    for (int i = 0; i < n_nets; ++i) {
-      MM_REQUIRE(nets[i].h_out, "mixer_fwd_seq: h_out [C][B][Hm] required");
-      MM_REQUIRE((uintptr_t)nets[i].gi % 16 == 0, "mixer_fwd_seq: gi must be 16-byte aligned");
-    }
-    mm::MixRecFwd rq;
-    rq.C = steps;
-    rq.win = mix_rec_win(steps, Hm, false);
-    rq.gi_st = q.gi_st;
-    rq.hout_st = (int64_t)B * Hm;
-    rq.save_st = q.save_st;
-    rq.reset_steps = reset_steps;
-    rq.trace = mm::debug_trace_buffer("MM_MIX_TRACE_FWD");
-    if (part == 3) {
-      *a_out = a;
-      *rq_out = rq;
-      return MM_OK;
-    }
-    if (part != 2) {
-      if (Hm == 32)
-        hipLaunchKernelGGL(mm::mixer_rec_fwd_kernel<32>, dim3(B, n_nets), dim3(256),
-                           mm::mix_rec_fwd_floats(Hm, rq.win) * 4, (hipStream_t)s, a, rq);
-      else
-        hipLaunchKernelGGL(mm::mixer_rec_fwd_kernel<64>, dim3(B, n_nets), dim3(256),
-                           mm::mix_rec_fwd_floats(Hm, rq.win) * 4, (hipStream_t)s, a, rq);
-      MM_HIP_CHECK(hipGetLastError());
-    }
-    if (part == 1) return MM_OK;
-    const int R = B * steps;
-    hipLaunchKernelGGL(mm::mixer_hyper_fwd_kernel, dim3((R + mm::MIX_SPB - 1) / mm::MIX_SPB, n_nets), dim3(256),
-                       mm::mix_hyper_fwd_floats(Hm, K1, N) * 4, (hipStream_t)s, a, R);
+  rc = mm::mix_seq_lds_setup();
+  if (rc) return rc;
+  const mm::MixFwdArgs a = mm::mix_fwd_args(nets, n_nets, B, N, S, Hm, K1, nullptr, nullptr);
+  if (part != MixSeqPart::Hyper) {
+    const mm::MixRecFwd rq = mm::mix_rec_fwd_args(B, N, Hm, K1, steps, reset_steps);
+    if (Hm == 32)
+      hipLaunchKernelGGL(mm::mixer_rec_fwd_kernel<32>, dim3(B, n_nets), dim3(256),
+                         mm::mix_rec_fwd_floats(Hm, rq.win) * 4, (hipStream_t)s, a, rq);
+    else
+      hipLaunchKernelGGL(mm::mixer_rec_fwd_kernel<64>, dim3(B, n_nets), dim3(256),
+                         mm::mix_rec_fwd_floats(Hm, rq.win) * 4, (hipStream_t)s, a, rq);
     MM_HIP_CHECK(hipGetLastError());
-    return MM_OK;
   }
-  const mm::MixSeqGeo g(Hm, K1, N);
-  hipLaunchKernelGGL(mm::mixer_fwd_seq_lds_kernel, dim3(B, n_nets), dim3(256), g.fwd_floats() * 4, (hipStream_t)s, a,
-                     q);
+  if (part == MixSeqPart::Rec) return MM_OK;
+  const int R = B * steps;
+  hipLaunchKernelGGL(mm::mixer_hyper_fwd_kernel, dim3((R + mm::MIX_SPB - 1) / mm::MIX_SPB, n_nets), dim3(256),
+                     mm::mix_hyper_fwd_floats(Hm, K1, N) * 4, (hipStream_t)s, a, R);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
 }
 
 int mm_mixer_fwd_seq(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const mm_mix_net* nets,
                      int32_t n_nets, int32_t steps, const uint8_t* reset_steps, mm_stream_t s) {
-  return mixer_fwd_seq_part(0, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
+  return mixer_fwd_seq_part(MixSeqPart::All, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
 }
 int mm_mixer_fwd_seq_rec(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const mm_mix_net* nets,
                          int32_t n_nets, int32_t steps, const uint8_t* reset_steps, mm_stream_t s) {
-  return mixer_fwd_seq_part(1, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
+  return mixer_fwd_seq_part(MixSeqPart::Rec, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
 }
 int mm_mixer_fwd_seq_hyper(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const mm_mix_net* nets,
                            int32_t n_nets, int32_t steps, const uint8_t* reset_steps, mm_stream_t s) {
-  return mixer_fwd_seq_part(2, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
+  return mixer_fwd_seq_part(MixSeqPart::Hyper, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s);
 }
 
 int mm_mixer_seq_split(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* ws,
                        int32_t steps) {
-  return (mm_mixer_fwd_seq_fits(B, N, Hm, K1) && mix_split_enabled() &&
-          mix_bwd_split_ok(B, N, S, Hm, K1, P, ws, steps)) ? 1 : 0;
+  return (mm_mixer_fwd_seq_fits(B, N, Hm, K1) && mix_bwd_split_ok(B, N, S, Hm, K1, P, ws, steps)) ? 1 : 0;
 }
 
 int mm_mixer_bwd(int32_t B, int32_t N, int32_t S, int32_t Hm, int32_t K1, const float* P, const float* save,
@@ -3224,16 +3012,7 @@ int mm_agent_mixer_bwd_seq(const mm_qnet_dims* d, const float* P, int64_t oWq, i
   if (rc) return rc;
   const int N = d->n_agents;
   const mm::MixBwdArgs ma = {mP, msave, qa, mdq, done, dhm, const_cast<float*>(dqa), mdelta, B, N, S, Hm, K1};
-  mm::MixRecBwd mq;
-  mq.C = steps;
-  mq.win = mix_rec_win(steps, Hm, true);
-  mq.save_st = (int64_t)B * mm::mix_save_dim(Hm, K1, N);
-  mq.delta_st = (int64_t)B * mm::mix_delta_dim(Hm, K1, N);
-  mq.done_st = B;
-  mq.done = done;
-  mq.xws = ws;
-  mq.ones = ones;
-  mq.trace = mm::debug_trace_buffer("MM_MIX_TRACE_BWD");
+  const mm::MixRecBwd mq = mm::mix_rec_bwd_args(B, N, Hm, K1, steps, done, ws, ones);
   const size_t sm = std::max(smem, mm::mix_rec_bwd_floats(Hm, mq.win) * 4);
   const int gx = (B + 3) / 4, na = gx * N;
 #define MM_PAIR(HA, HMX)                                                                                          \
@@ -3253,8 +3032,8 @@ int mm_lrn_seq_windows(const mm_qnet_dims* d, int32_t Hm, int32_t steps, int32_t
   MM_REQUIRE((d->h == 32 || d->h == 64) && d->n_actions <= 64, "lrn_seq_windows: needs H in {32, 64} and A <= 64");
   MM_REQUIRE(Hm == 0 || mm::mix_rec_supported(Hm), "lrn_seq_windows: Hm must be 0 (no mixer recurrence), 32 or 64");
   out[0] = agent_bwd_seq_win(d->h, d->n_actions, steps);
-  out[1] = Hm ? mix_rec_win(steps, Hm, true) : steps;
-  out[2] = Hm ? mix_rec_win(steps, Hm, false) : steps;
+  out[1] = Hm ? mm::mix_rec_win(steps, Hm, true) : steps;
+  out[2] = Hm ? mm::mix_rec_win(steps, Hm, false) : steps;
   return MM_OK;
 }
 
@@ -3272,16 +3051,6 @@ int mm_agent_bwd(const mm_qnet_dims* d, const float* P, int64_t oWq, int64_t oWh
     return MM_OK;
   }
   hipLaunchKernelGGL(mm::agent_bwd_kernel, dim3((pairs + 3) / 4), dim3(256), 0, (hipStream_t)s, a);
-  MM_HIP_CHECK(hipGetLastError());
-  return MM_OK;
-}
-
-int mm_outer_reduce(const mm_outer_args* x, mm_stream_t s) {
-  MM_REQUIRE(x && x->M >= 0 && x->R > 0 && x->Cc > 0 && x->groups > 0, "outer_reduce: bad args");
-  mm::OuterArgs a = {x->U, x->u_g, x->u_m, x->V, x->v_g, x->v_m, x->v_off, x->v_reset, x->dW, x->w_g,
-                     x->db, x->b_g, x->M, x->R, x->Cc, x->accumulate};
-  dim3 grid((x->Cc + 31) / 32, (x->R + 31) / 32, x->groups);
-  hipLaunchKernelGGL(mm::outer_reduce_kernel, grid, dim3(256), 0, (hipStream_t)s, a);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
 }

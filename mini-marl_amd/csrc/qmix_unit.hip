@@ -85,7 +85,7 @@ static size_t rec_pair_lds(int32_t Hm, int32_t steps) {
 static bool rec_pair_ok(const mm_qnet_dims* d, int32_t B, int32_t N, int32_t Hm, int32_t K1, int32_t steps) {
   if (!pair_dims_ok(d) || d->n_agents != N) return false;
   const int64_t agent_blocks = 2 * ((B + 31) / 32) * (int64_t)N;
-  return agent_blocks < 512 && mix_split_enabled() && mix_rec_supported(Hm) && mm_mixer_fwd_seq_fits(B, N, Hm, K1) &&
+  return agent_blocks < 512 && mix_rec_supported(Hm) && mm_mixer_fwd_seq_fits(B, N, Hm, K1) &&
          rec_pair_lds(Hm, steps) <= 160 * 1024;
 }
 
@@ -135,9 +135,11 @@ int mm_mixer_bwd_seq_hyper_per(int32_t B, int32_t N, int32_t S, int32_t Hm, int3
                      mm::mix_hyper_bwd_floats(Hm, K1, N) * 4 + mm::kPerSmallLds <= mm::kMixSeqLds;
   if (small) {
     const mm::PerUpd pu = {per->tree, per->cap, nodes, td, per->st, batch, (float)per->eps};
-    return mixer_bwd_seq_part(1, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps, s, &pu);
+    return mixer_bwd_seq_part(MixSeqPart::Hyper, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws,
+                              steps, s, &pu);
   }
-  const int rc = mixer_bwd_seq_part(1, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta, ws, steps, s);
+  const int rc = mixer_bwd_seq_part(MixSeqPart::Hyper, B, N, S, Hm, K1, P, save, qa, dq, done, ones, dhm, dqa, delta,
+                                    ws, steps, s);
   if (rc) return rc;
   return mm_per_update(per, nodes, td, batch, s);
 }
@@ -216,16 +218,7 @@ int mm_agent_mixer_pre(const mm_qnet_dims* d, const float* packed0, const mm_qfw
   if (rc) return rc;
   p0.nblocks = (int)((rows + 31) / 32) * N;
   p1.nblocks = p0.nblocks;
-  mm::MixGiArgs a;
-  a.net[0] = {mP0, s_off0, gi0};
-  a.net[1] = {mP1, s_off1, gi1};
-  a.obs = obs;
-  a.reset_obs = reset_obs;
-  a.R = (int)rows;
-  a.S = S;
-  a.Hm = Hm;
-  a.K1 = K1;
-  a.N = N;
+  const mm::MixGiArgs a = mm::mix_gi_args((int)rows, N, S, Hm, K1, obs, reset_obs, mP0, s_off0, gi0, mP1, s_off1, gi1);
   const int gx = (int)((rows + 31) / 32), gy = (3 * Hm + 31) / 32, n_gi = gx * gy * 2;
   using PG = mm::PairGeo<64, 64, 64>;
   if ((d->n_actions + 31) / 32 == 1)
@@ -251,10 +244,10 @@ int mm_agent_mixer_rec_seq(const mm_qnet_dims* d, const float* packed0, const mm
   if (rc) return rc;
   p0.nblocks = (p0.E + 31) / 32 * p0.N;
   p1.nblocks = (p1.E + 31) / 32 * p1.N;
-  mm::MixFwdArgs ma;
-  mm::MixRecFwd mq;
-  rc = mixer_fwd_seq_part(3, B, N, S, Hm, K1, nets, n_nets, steps, reset_steps, s, &ma, &mq);
+  rc = mixer_fwd_seq_check(B, N, Hm, K1, nets, n_nets, steps, reset_steps);
   if (rc) return rc;
+  const mm::MixFwdArgs ma = mm::mix_fwd_args(nets, n_nets, B, N, S, Hm, K1, nullptr, nullptr);
+  const mm::MixRecFwd mq = mm::mix_rec_fwd_args(B, N, Hm, K1, steps, reset_steps);
   const size_t sm = mm::rec_pair_lds(Hm, steps);
   const int n_agent = p0.nblocks + p1.nblocks;
   using PG = mm::PairGeo<64, 64, 64>;

@@ -22,6 +22,7 @@ Adam moments alike; phi starts at the next multiple of 4 floats), the layout the
 """
 import ctypes
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -94,6 +95,18 @@ class Mixer:
         return {_MIX_FMT[k]: self.view(k, host).clone() for k in MIX_KEYS}
 
 
+class _Plan(NamedTuple):
+    """The launch path of one update (QLearner._plan)."""
+    seq: bool             # agent REC as one chunk-sequence launch (else one launch per step, mixers in between)
+    split: bool           # mixer recurrence and hypernet pass as separate launches, forward and backward
+    pair_fwd: bool        # agent and mixer forward chains in shared grids (mm_agent_mixer_pre / _rec_seq)
+    fwd_side: bool        # the mixer's state projection + recurrence on the side stream (else in line)
+    mixer_fwd: Optional[str]   # "split", "seq" (mm_mixer_fwd_seq in line), "steps" (mm_mixer_fwd per step); None: VDN
+    agent_bwd_seq: bool   # agent BPTT as one launch for all C steps (else one per step)
+    pair_bwd: bool        # agent BPTT and the mixer recurrence's backward in one launch
+    h3_pre: bool          # the opt-in fp16x3 agent PRE
+
+
 class QLearner:
     """mode "qmix" (Train_dqn), "vdn" (Target_Dqn: Q_tot = sum_i Q_i, no mixer) or "qmix_min"
     (qmix/qmix.py train: Huber loss, unweighted sum target, separate agent / mixer clipping)."""
@@ -124,7 +137,6 @@ class QLearner:
         # the forward's agent and mixer chains in shared grids (mm_agent_mixer_pre / mm_agent_mixer_rec_seq) where
         # the shapes allow: no fork / join at all (pair_fwd=False: the side stream above)
         self._pair_fwd = bool(pair_fwd)
-        self._pair_ok = None
         self._per_next = None          # the PER of the update being recorded (sample_and_grads -> compute_grads)
         self._per_done = False         # its priority update already issued (with the hypernet backward)
         self.fast_pre = False           # opt-in: the fp16x3 agent PRE (not at the fp32 gradient bar, see compute_grads)
@@ -237,11 +249,10 @@ class QLearner:
             self.gi_b = torch.zeros(C, B, 3 * Hm, **f32)
             self.gi_t = torch.zeros(C, B, 3 * Hm, **f32)
         # split-M outer-reduce partials: the job geometry is fixed, size it once (no launches here)
-        jobs = []
         zero = ctypes.c_void_p(0)
-        self._agent_wgrad(None, None, zero, zero, C * B, jobs)
+        jobs = self._agent_wgrad_jobs(zero, zero, C * B)
         if self.has_mixer:
-            self._mixer_wgrad(None, None, zero, zero, C * B, jobs)
+            jobs += self._mixer_wgrad_jobs(zero, zero, C * B)
         arr = (OuterArgs * len(jobs))(*jobs)
         self._opart = torch.zeros(int(lib().mm_outer_reduce_batch_partial(arr, len(jobs))), **f32)
 
@@ -294,217 +305,307 @@ class QLearner:
             self._deps_host = self.double_eps
 
     _deps_host = None
+    _plan_key = None
+
+    def _plan(self):
+        """The launch path of an update (``_Plan``): fixed by the shapes and the constructor's switches, but for
+        ``seq`` and ``fast_pre``, which may be assigned later; rebuilt only when one of those two changed."""
+        seq, fast_pre = key = bool(self.seq), bool(self.fast_pre)
+        if self._plan_key == key:
+            return self._plan_val
+        L, B, C, N, mx = lib(), self.B, self.C, self.N, self.mix
+        split, pair_fwd, mixer_fwd = False, False, None
+        if self.has_mixer:
+            # sequence path with both split mixer kernels available (B < 512, aligned weights and workspace)
+            split = bool(seq and B < 512 and L.mm_mixer_seq_split(B, N, mx.S, mx.Hm, mx.K1, ptr(mx.flat),
+                                                                   ptr(self.mxws), C))
+            # QMIX, exact-f32 state projection, the B = 32 shapes
+            pair_fwd = bool(split and self._pair_fwd and not self.mixer_fp16 and
+                            L.mm_agent_mixer_pair_supported(ctypes.byref(self.beh.dims), B, C, N, mx.S, mx.Hm,
+                                                            mx.K1) == 3)
+            seq_fits = seq and L.mm_mixer_fwd_seq_fits(B, N, mx.Hm, mx.K1)
+            mixer_fwd = "split" if split else "seq" if seq_fits else "steps"
+        agent_bwd_seq = bool(seq and B < 512 and self.H in (32, 64))
+        self._plan_key = key
+        self._plan_val = _Plan(seq=seq, split=split, pair_fwd=pair_fwd,
+                               fwd_side=bool(split and self._fwd_side and not pair_fwd), mixer_fwd=mixer_fwd,
+                               agent_bwd_seq=agent_bwd_seq, pair_bwd=bool(split and agent_bwd_seq and self._pair_bwd),
+                               h3_pre=bool(self.mixer_fp16 and C * B >= 2048 and fast_pre))
+        return self._plan_val
+
+    def _mixer_split(self):
+        return self._plan().split
+
+    def _fwd_pair(self):
+        return self._plan().pair_fwd
+
+    def _uses_h3(self):
+        """Whether this learner's own forward reads the fp16x3 image (the opt-in fast PRE)."""
+        return self._plan().h3_pre
 
     def compute_grads(self, obs_base, reset_obs_ptr):
         """Forward C steps, loss, BPTT and all weight gradients into self.Gr (all async)."""
         L, s = lib(), stream_handle(self.dev)
         if not torch.cuda.is_current_stream_capturing():
             self._push_double_eps()
-        B, C, N, H, D = self.B, self.C, self.N, self.H, self.D
-        CB = C * B
+        plan = self._plan()
         self._pack(self.beh, s)
         self._pack(self.tgt, s)
         obs_p = ctypes.c_void_p(obs_base) if isinstance(obs_base, int) else ptr(obs_base)
         reset_p = ctypes.c_void_p(reset_obs_ptr) if isinstance(reset_obs_ptr, int) else ptr(reset_obs_ptr)
-        ND = N * D
-        split = self._mixer_split()
-        pair = bool(split) and self._fwd_pair()
-        side = self._side_stream() if split else None
-        fwd_side = split and self._fwd_side and not pair
-        if fwd_side:
+        self._forward(plan, L, s, obs_p, reset_p)
+        # ---- loss, dQ_tot, priorities
+        check(L.mm_lrn_loss_ex(self.B, self.C, self.N, self.gamma, ptr(self.rew), ptr(self.done), ptr(self.isw),
+                               ptr(self.qtot), ptr(self.qtot_t), self.loss_flags, ptr(self.qa), ptr(self.maxq),
+                               ptr(self.dq), ptr(self.dqa), ptr(self.loss_parts), ptr(self.td_last), ptr(self.loss),
+                               s), "loss")
+        self._backward(plan, L, s)
+        self._weight_grads(L, s, obs_p, reset_p)
+
+    # ---- forward over the chunk: the non-recurrent part (layers 1-2, W_ih x2) of every (t, b) of both nets in
+    # ONE launch (PRE), then the recurrent part (W_hh h, gates, Q head: REC), then the mixers
+    def _forward(self, plan, L, s, obs_p, reset_p):
+        B, C, N, D = self.B, self.C, self.N, self.D
+        CB = C * B
+        dims, mx = ctypes.byref(self.beh.dims), self.mix
+        cur = torch.cuda.current_stream(self.dev)
+        s_m = s
+        if plan.fwd_side:
             # two streams (captured as a fork / join in the update graph): the mixer's state projection and its
             # GRU recurrence need no agent Q, so they run beside the agent PRE / REC chain
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            s_m = ctypes.c_void_p(side.cuda_stream)
-        else:
-            s_m = s
-        if self.has_mixer and not pair:
+            self._side_stream().wait_stream(cur)
+            s_m = ctypes.c_void_p(self._side_stream().cuda_stream)
+        if self.has_mixer and not plan.pair_fwd:
             # mixer GRU input projections of every (t, b) for both mixers: one MFMA launch
-            mx = self.mix
             gi_fn = L.mm_mixer_gi_f16 if self.mixer_fp16 else L.mm_mixer_gi
             check(gi_fn(CB, N, mx.S, mx.Hm, mx.K1, obs_p, reset_p, ptr(mx.flat), ptr(self.s_off),
                         ptr(self.gi_b), ptr(self.tmix.flat), ptr(self.s2_off), ptr(self.gi_t), s_m), "mixer gi")
-            if split:
-                self._mixer_seq_call(L, L.mm_mixer_fwd_seq_rec, s_m, "mixer fwd seq (recurrence)")
-        # ---- forward over the chunk: the non-recurrent part (layers 1-2, W_ih x2) of every (t, b) of
-        # both nets in ONE launch, then one recurrent step (W_hh h, gates, Q head) per t
-        pb, pt = QFwdIO(), QFwdIO()
-        for io, off, gi in ((pb, self.s_off, self.gi_ab), (pt, self.s2_off, self.gi_at)):
-            io.obs, io.obs_se, io.obs_sa, io.obs_off = obs_p.value, 1, D, 0
-            io.obs_row = off.data_ptr()
-            io.reset_obs = reset_p.value
-            io.h_in = self.hb.data_ptr()       # unused by PRE
-            io.gi = gi.data_ptr()
+            if plan.split:
+                self._mixer_seq_call(L.mm_mixer_fwd_seq_rec, s_m, "mixer fwd seq (recurrence)")
+        pb = self._pre_io(obs_p, reset_p, self.s_off, self.gi_ab)
+        pt = self._pre_io(obs_p, reset_p, self.s2_off, self.gi_at)
         pb.save = self.asave.data_ptr()
-        # the agent PRE stays exact f32 in every mode: on the fp16x3 image (mm_agent_q_pre2_h3) the split weights'
-        # lo parts of a wide layer 1 (D = 300, |W| ~ 0.06) fall into f16's subnormal range, and the few ReLU masks that
-        # flip against f32 put ~0.3 % of dW1 / dW2 outside the fp32 bar (test_learner_cfg5_benched_path_vs_oracle)
-        pre_fn = L.mm_agent_q_pre2_h3 if (self.mixer_fp16 and CB >= 2048 and self.fast_pre) else L.mm_agent_q_pre2
-        if pair:
+        if plan.pair_fwd:
             # + the mixers' state projection (mm_mixer_gi) in the same grid
-            mx = self.mix
-            check(L.mm_agent_mixer_pre(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(pb),
-                                       ptr(self.tgt.packed), ctypes.byref(pt), CB, N, mx.S, mx.Hm, mx.K1, obs_p,
-                                       reset_p, ptr(mx.flat), ptr(self.s_off), ptr(self.gi_b), ptr(self.tmix.flat),
-                                       ptr(self.s2_off), ptr(self.gi_t), s), "learner fwd pre + mixer gi")
+            check(L.mm_agent_mixer_pre(dims, ptr(self.beh.packed), ctypes.byref(pb), ptr(self.tgt.packed),
+                                       ctypes.byref(pt), CB, N, mx.S, mx.Hm, mx.K1, obs_p, reset_p, ptr(mx.flat),
+                                       ptr(self.s_off), ptr(self.gi_b), ptr(self.tmix.flat), ptr(self.s2_off),
+                                       ptr(self.gi_t), s), "learner fwd pre + mixer gi")
         else:
-            check(pre_fn(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(pb), CB,
-                         ptr(self.tgt.packed), ctypes.byref(pt), CB, s), "learner fwd pre")
+            # exact f32 unless opted in: on the fp16x3 image (mm_agent_q_pre2_h3) the split weights' lo parts of a wide
+            # layer 1 (D = 300, |W| ~ 0.06) fall into f16's subnormal range, and the few ReLU masks that flip against
+            # f32 put ~0.3 % of dW1 / dW2 outside the fp32 bar (test_learner_cfg5_benched_path_vs_oracle)
+            pre_fn = L.mm_agent_q_pre2_h3 if plan.h3_pre else L.mm_agent_q_pre2
+            check(pre_fn(dims, ptr(self.beh.packed), ctypes.byref(pb), CB, ptr(self.tgt.packed), ctypes.byref(pt),
+                         CB, s), "learner fwd pre")
         if self.double:   # the double net (behavior weights) on s'
-            pd = QFwdIO()
-            pd.obs, pd.obs_se, pd.obs_sa, pd.obs_off = obs_p.value, 1, D, 0
-            pd.obs_row = self.s2_off.data_ptr()
-            pd.reset_obs = reset_p.value
-            pd.h_in = self.hb.data_ptr()
-            pd.gi = self.gi_ad.data_ptr()
-            check(L.mm_agent_q_pre2(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(pd), CB,
-                                    None, None, 0, s), "learner fwd pre (double)")
-        gstep = 4 * B * N * 3 * H
-        if self.double and self._draws is None:
-            self.dctr.add_(C)             # stream-ordered: captured into the update graph
-        if self.seq:
-            self._forward_seq(L, s, obs_p, reset_p, split, join=fwd_side, pair=pair)
-        for t in range(0 if not self.seq else C, C):
-            ib, it = QFwdIO(), QFwdIO()
-            for io, h, gi in ((ib, self.hb, self.gi_ab), (it, self.ht, self.gi_at)):
-                io.obs = obs_p.value               # unused by REC
-                io.h_in = h[t % 2].data_ptr()
-                io.h_out = h[(t + 1) % 2].data_ptr()
-                io.hin_se = io.hout_se = N * H
-                io.hin_sa = io.hout_sa = H
-                io.hin_sf = io.hout_sf = 1
-                io.reset = self.ones8.data_ptr() if t == 0 else self.done8.data_ptr() + (t - 1) * B
-                io.gi = gi.data_ptr() + t * gstep
-            ib.mode = MM_Q_GATHER
-            ib.act_in, ib.act_se = self.acts.data_ptr() + 4 * t * B * N, N
-            ib.qsel_out = self.qa[t].data_ptr()
-            ib.save = self.asave[t].data_ptr()
-            it.mode = MM_Q_MAX
-            it.qsel_out = self.maxq[t].data_ptr()
-            if self.double:
-                # behavior on s_t + the double net's eps-greedy actions on s'_t, then the target net's
-                # Q at those actions (Target_Double_Dqn, vdn/_train.py:121-130)
-                idd = QFwdIO()
-                idd.obs = obs_p.value
-                idd.h_in, idd.h_out = self.hd[t % 2].data_ptr(), self.hd[(t + 1) % 2].data_ptr()
-                idd.hin_se = idd.hout_se = N * H
-                idd.hin_sa = idd.hout_sa = H
-                idd.hin_sf = idd.hout_sf = 1
-                idd.reset = it.reset
-                idd.gi = self.gi_ad.data_ptr() + t * gstep
-                idd.mode = MM_Q_ACT
-                idd.act_out = self.act_d[t].data_ptr()
-                idd.qsel_out = self.qsel_d[t].data_ptr()
-                idd.epsilon = float(self.double_eps)
-                idd.eps_ptr = self.deps.data_ptr()
-                if self._draws is not None:
-                    idd.u = self._draws[0][t].data_ptr()
-                    idd.rand_act = self._draws[1][t].data_ptr()
-                else:
-                    idd.seed = self.double_seed
-                    idd.counter_ptr = self.dctr.data_ptr() + 8 * t
-                check(L.mm_agent_q_rec2(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(ib), B,
-                                        ptr(self.beh.packed), ctypes.byref(idd), B, s), "learner fwd rec")
-                it.mode = MM_Q_GATHER
-                it.act_in, it.act_se = self.act_d[t].data_ptr(), N
-                check(L.mm_agent_q_rec2(ctypes.byref(self.beh.dims), ptr(self.tgt.packed), ctypes.byref(it), B,
-                                        None, None, 0, s), "learner fwd rec (target at double actions)")
+            pd = self._pre_io(obs_p, reset_p, self.s2_off, self.gi_ad)
+            check(L.mm_agent_q_pre2(dims, ptr(self.beh.packed), ctypes.byref(pd), CB, None, None, 0, s),
+                  "learner fwd pre (double)")
+            if self._draws is None:
+                self.dctr.add_(C)             # stream-ordered: captured into the update graph
+        if not plan.seq:
+            # one REC launch per step, each followed by that step's mixers
+            for t in range(C):
+                self._rec_step(L, s, t, obs_p)
+                if self.has_mixer:
+                    self._mixer_step(L, s, t, obs_p, reset_p)
+            return
+        self._rec_seq(plan, L, s, obs_p)
+        if plan.mixer_fwd == "split":
+            # join the mixer recurrence (side stream), then the hypernet pass over the agents' Q
+            if plan.fwd_side:
+                cur.wait_stream(self._side_stream())
+            self._mixer_seq_call(L.mm_mixer_fwd_seq_hyper, s, "mixer fwd seq (hypernets)")
+        elif plan.mixer_fwd == "seq":
+            # the recurrence and the hypernet pass in line (bit-identical to the per-step launches below)
+            self._mixer_seq_call(L.mm_mixer_fwd_seq, s, "mixer fwd seq")
+        elif plan.mixer_fwd == "steps":
+            # per-step launches on the REC outputs (B >= 512: 8 samples per block share the weight reads)
+            for t in range(C):
+                self._mixer_step(L, s, t, obs_p, reset_p)
+
+    def _pre_io(self, obs_p, reset_p, off, gi):
+        io = QFwdIO()
+        io.obs, io.obs_se, io.obs_sa, io.obs_off = obs_p.value, 1, self.D, 0
+        io.obs_row = off.data_ptr()
+        io.reset_obs = reset_p.value
+        io.h_in = self.hb.data_ptr()       # unused by PRE
+        io.gi = gi.data_ptr()
+        return io
+
+    def _rec_io(self, obs_p, h, gi, t):
+        B, N, H = self.B, self.N, self.H
+        io = QFwdIO()
+        io.obs = obs_p.value               # unused by REC
+        if t is None:
+            io.gi = gi.data_ptr()
+            return io
+        io.h_in, io.h_out = h[t % 2].data_ptr(), h[(t + 1) % 2].data_ptr()
+        io.hin_se = io.hout_se = N * H
+        io.hin_sa = io.hout_sa = H
+        io.hin_sf = io.hout_sf = 1
+        io.reset = self.ones8.data_ptr() if t == 0 else self.done8.data_ptr() + (t - 1) * B
+        io.gi = gi.data_ptr() + t * 4 * B * N * 3 * H
+        return io
+
+    def _rec_ios(self, obs_p, t=None):
+        """REC arguments of the behavior / target nets: chunk step t alone (hidden ping-pong, reset where the
+        previous step was done), or with t = None the step-0 pointers for a chunk-sequence launch."""
+        ib, it = self._rec_io(obs_p, self.hb, self.gi_ab, t), self._rec_io(obs_p, self.ht, self.gi_at, t)
+        k = 0 if t is None else t
+        ib.mode = MM_Q_GATHER
+        ib.act_in, ib.act_se = self.acts.data_ptr() + 4 * k * self.B * self.N, self.N
+        ib.qsel_out = self.qa[k].data_ptr()
+        ib.save = self.asave[k].data_ptr()
+        it.mode = MM_Q_MAX
+        it.qsel_out = self.maxq[k].data_ptr()
+        return ib, it
+
+    def _rec_step(self, L, s, t, obs_p):
+        B, N = self.B, self.N
+        dims = ctypes.byref(self.beh.dims)
+        ib, it = self._rec_ios(obs_p, t)
+        if not self.double:
+            check(L.mm_agent_q_rec2(dims, ptr(self.beh.packed), ctypes.byref(ib), B, ptr(self.tgt.packed),
+                                    ctypes.byref(it), B, s), "learner fwd rec")
+            return
+        # behavior on s_t + the double net's eps-greedy actions on s'_t, then the target net's
+        # Q at those actions (Target_Double_Dqn, vdn/_train.py:121-130)
+        idd = self._rec_io(obs_p, self.hd, self.gi_ad, t)
+        idd.mode = MM_Q_ACT
+        idd.act_out = self.act_d[t].data_ptr()
+        idd.qsel_out = self.qsel_d[t].data_ptr()
+        idd.epsilon = float(self.double_eps)
+        idd.eps_ptr = self.deps.data_ptr()
+        if self._draws is not None:
+            idd.u = self._draws[0][t].data_ptr()
+            idd.rand_act = self._draws[1][t].data_ptr()
+        else:
+            idd.seed = self.double_seed
+            idd.counter_ptr = self.dctr.data_ptr() + 8 * t
+        check(L.mm_agent_q_rec2(dims, ptr(self.beh.packed), ctypes.byref(ib), B, ptr(self.beh.packed),
+                                ctypes.byref(idd), B, s), "learner fwd rec")
+        it.mode = MM_Q_GATHER
+        it.act_in, it.act_se = self.act_d[t].data_ptr(), N
+        check(L.mm_agent_q_rec2(dims, ptr(self.tgt.packed), ctypes.byref(it), B, None, None, 0, s),
+              "learner fwd rec (target at double actions)")
+
+    def _rec_seq(self, plan, L, s, obs_p):
+        """REC of both nets over all C steps in one chunk-sequence launch."""
+        B, C, N, mx = self.B, self.C, self.N, self.mix
+        dims = ctypes.byref(self.beh.dims)
+        ib, it = self._rec_ios(obs_p)
+        if plan.pair_fwd:
+            # + the mixers' GRU over the state (mm_mixer_fwd_seq_rec) in the same grid
+            check(L.mm_agent_mixer_rec_seq(dims, ptr(self.beh.packed), ctypes.byref(ib), ptr(self.tgt.packed),
+                                           ctypes.byref(it), B, C, ptr(self.done8), N, mx.S, mx.Hm, mx.K1,
+                                           self._mixer_step_nets(), 2, ptr(self.done8), s),
+                  "rec seq + mixer recurrence")
+        else:
+            check(L.mm_agent_q_rec_seq2(dims, ptr(self.beh.packed), ctypes.byref(ib), B, ptr(self.tgt.packed),
+                                        ctypes.byref(it), B, C, ptr(self.done8), s), "rec seq")
+
+    def _mixer_step_nets(self, t=None):
+        """Both mixers' arrays for chunk step t alone (hidden ping-pong, reset where the previous step was done), or
+        with t = None the step-0 pointers for the chunk-sequence launches (which write the hidden sequences)."""
+        B, k = self.B, 0 if t is None else t
+        nets = (MixNetIO * 2)()
+        for i, (Pm, q, off, h, qt, sv, gi) in enumerate(
+                ((self.mix.flat, self.qa[k], self.s_off, self.hm, self.qtot[k], self.msave[k], self.gi_b[k]),
+                 (self.tmix.flat, self.maxq[k], self.s2_off, self.hmt, self.qtot_t[k], None, self.gi_t[k]))):
+            n = nets[i]
+            n.P, n.q, n.gi, n.qtot = Pm.data_ptr(), q.data_ptr(), gi.data_ptr(), qt.data_ptr()
+            n.save = sv.data_ptr() if sv is not None else None
+            n.reset = self.ones8.data_ptr() if k == 0 else self.done8.data_ptr() + (k - 1) * B
+            if t is None:    # (the sequence kernels read no state: s_off is unused)
+                n.s_off, n.h_in, n.h_out = self.s_off.data_ptr(), self.hm[0].data_ptr(), self.mhseq[i].data_ptr()
             else:
-                check(L.mm_agent_q_rec2(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(ib), B,
-                                        ptr(self.tgt.packed), ctypes.byref(it), B, s), "learner fwd rec")
-            if self.has_mixer:
-                mx = self.mix
-                nets = (MixNetIO * 2)()
-                for k, (P, q, off, h, qt, sv, gi) in enumerate(
-                        ((self.mix.flat, self.qa[t], self.s_off, self.hm, self.qtot[t], self.msave[t], self.gi_b[t]),
-                         (self.tmix.flat, self.maxq[t], self.s2_off, self.hmt, self.qtot_t[t], None, self.gi_t[t]))):
-                    n = nets[k]
-                    n.P, n.q, n.gi = P.data_ptr(), q.data_ptr(), gi.data_ptr()
-                    n.s_off = off.data_ptr() + 8 * t * B
-                    n.h_in, n.h_out = h[t % 2].data_ptr(), h[(t + 1) % 2].data_ptr()
-                    n.reset = self.ones8.data_ptr() if t == 0 else self.done8.data_ptr() + (t - 1) * B
-                    n.qtot = qt.data_ptr()
-                    n.save = sv.data_ptr() if sv is not None else None
-                check(L.mm_mixer_fwd(B, N, mx.S, mx.Hm, mx.K1, obs_p, reset_p, nets, 2, s), "mixer fwd")
-        # ---- loss, dQ_tot, priorities
-        check(L.mm_lrn_loss_ex(B, C, N, self.gamma, ptr(self.rew), ptr(self.done), ptr(self.isw), ptr(self.qtot),
-                               ptr(self.qtot_t), self.loss_flags, ptr(self.qa), ptr(self.maxq), ptr(self.dq),
-                               ptr(self.dqa), ptr(self.loss_parts), ptr(self.td_last), ptr(self.loss), s), "loss")
-        # ---- backward through time (data-gradient chains only)
-        agent_seq = self.seq and B < 512 and self.H in (32, 64)
-        pair_bwd = bool(split) and agent_seq and self.has_mixer and self._pair_bwd
-        o = self.beh.offs
-        P = self.P
-        if self.seq:
-            if self.has_mixer:
-                mx = self.mix
-                margs = (B, N, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.msave), ptr(self.qa), ptr(self.dq),
-                         ptr(self.done), ptr(self.ones_f), ptr(self.dhm), ptr(self.dqa), ptr(self.mdelta),
-                         ptr(self.mxws), C)
-                if split:
-                    # the hypernet pass (-> dqa for the agents), then the mixer recurrence's backward beside the
-                    # agent BPTT: one shared launch below (mm_agent_mixer_bwd_seq), or the side stream joined
-                    # before the weight gradients. A sampled update's priority update rides along (the loss's TDs
-                    # are final): one more block of the hypernet launch
-                    if self._per_next is not None:
-                        check(L.mm_mixer_bwd_seq_hyper_per(*margs, self._per_next._h, ptr(self.nodes),
-                                                           ptr(self.td_last), self.B, s),
-                              "mixer bwd seq (hypernets) + priority update")
-                        self._per_done = True
-                    else:
-                        check(L.mm_mixer_bwd_seq_hyper(*margs, s), "mixer bwd seq (hypernets)")
-                    if not pair_bwd:
-                        side.wait_stream(torch.cuda.current_stream(self.dev))
-                        check(L.mm_mixer_bwd_seq_rec(*margs, s_m), "mixer bwd seq (recurrence)")
+                n.s_off = off.data_ptr() + 8 * t * B
+                n.h_in, n.h_out = h[t % 2].data_ptr(), h[(t + 1) % 2].data_ptr()
+        return nets
+
+    def _mixer_step(self, L, s, t, obs_p, reset_p):
+        mx = self.mix
+        check(L.mm_mixer_fwd(self.B, self.N, mx.S, mx.Hm, mx.K1, obs_p, reset_p, self._mixer_step_nets(t), 2, s),
+              "mixer fwd")
+
+    def _mixer_seq_call(self, fn, s, what):
+        mx = self.mix
+        check(fn(self.B, self.N, mx.S, mx.Hm, mx.K1, self._mixer_step_nets(), 2, self.C, ptr(self.done8), s), what)
+
+    # ---- backward through time (data-gradient chains only)
+    def _backward(self, plan, L, s):
+        B, C, N, mx = self.B, self.C, self.N, self.mix
+        dims, o, P = ctypes.byref(self.beh.dims), self.beh.offs, self.P
+        cur = torch.cuda.current_stream(self.dev)
+        # no shared launch: the mixer recurrence forks off the hypernet pass (onto the side stream where the forward
+        # uses it, else in line) and joins before the weight gradients
+        fork_rec = plan.split and not plan.pair_bwd
+        if plan.seq and self.has_mixer:
+            margs = (B, N, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.msave), ptr(self.qa), ptr(self.dq),
+                     ptr(self.done), ptr(self.ones_f), ptr(self.dhm), ptr(self.dqa), ptr(self.mdelta),
+                     ptr(self.mxws), C)
+            if not plan.split:
+                check(L.mm_mixer_bwd_seq(*margs, s), "mixer bwd seq")
+            else:
+                # the hypernet pass (-> dqa for the agents), then the mixer recurrence's backward beside the
+                # agent BPTT: one shared launch below (mm_agent_mixer_bwd_seq), or forked. A sampled update's
+                # priority update rides along (the loss's TDs are final): one more block of the hypernet launch
+                if self._per_next is not None:
+                    check(L.mm_mixer_bwd_seq_hyper_per(*margs, self._per_next._h, ptr(self.nodes),
+                                                       ptr(self.td_last), self.B, s),
+                          "mixer bwd seq (hypernets) + priority update")
+                    self._per_done = True
                 else:
-                    check(L.mm_mixer_bwd_seq(*margs, s), "mixer bwd seq")
+                    check(L.mm_mixer_bwd_seq_hyper(*margs, s), "mixer bwd seq (hypernets)")
+                if fork_rec:
+                    side = self._side_stream()
+                    side.wait_stream(cur)
+                    s_m = ctypes.c_void_p(side.cuda_stream) if plan.fwd_side else s
+                    check(L.mm_mixer_bwd_seq_rec(*margs, s_m), "mixer bwd seq (recurrence)")
         self._per_next = None
-        if pair_bwd:
+        aseq = (dims, ptr(P), o[8], o[5], B, ptr(self.asave), ptr(self.acts), ptr(self.dqa), ptr(self.done),
+                ptr(self.ones_f), ptr(self.dh), ptr(self.dgi), ptr(self.dgh), ptr(self.dqv), C)
+        if plan.pair_bwd:
             # the agent BPTT chain and the mixer recurrence's backward sharing one grid
-            mx = self.mix
-            check(L.mm_agent_mixer_bwd_seq(ctypes.byref(self.beh.dims), ptr(P), o[8], o[5], B, ptr(self.asave),
-                                           ptr(self.acts), ptr(self.dqa), ptr(self.done), ptr(self.ones_f),
-                                           ptr(self.dh), ptr(self.dgi), ptr(self.dgh), ptr(self.dqv), C, mx.S, mx.Hm,
-                                           mx.K1, ptr(mx.flat), ptr(self.msave), ptr(self.qa), ptr(self.dq),
-                                           ptr(self.dhm), ptr(self.mdelta), ptr(self.mxws), s), "agent+mixer bwd seq")
-        elif agent_seq:
+            check(L.mm_agent_mixer_bwd_seq(*aseq, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.msave), ptr(self.qa),
+                                           ptr(self.dq), ptr(self.dhm), ptr(self.mdelta), ptr(self.mxws), s),
+                  "agent+mixer bwd seq")
+        elif plan.agent_bwd_seq:
             # the agent BPTT chain over all C steps in one launch (W_hh in LDS, dh carried in registers)
-            check(L.mm_agent_bwd_seq(ctypes.byref(self.beh.dims), ptr(P), o[8], o[5], B, ptr(self.asave),
-                                     ptr(self.acts), ptr(self.dqa), ptr(self.done), ptr(self.ones_f), ptr(self.dh),
-                                     ptr(self.dgi), ptr(self.dgh), ptr(self.dqv), C, s), "agent bwd seq")
-        for t in range(C - 1, -1, -1):
-            if agent_seq:
-                break
-            dn = self.ones_f if t == C - 1 else self.done[t * B:(t + 1) * B]
-            if self.has_mixer and not self.seq:
-                mx = self.mix
-                check(L.mm_mixer_bwd(B, N, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.msave[t]), ptr(self.qa[t]),
-                                     ptr(self.dq[t]), ptr(dn), ptr(self.dhm), ptr(self.dqa[t]), ptr(self.mdelta[t]),
-                                     s), "mixer bwd")
-            check(L.mm_agent_bwd(ctypes.byref(self.beh.dims), ptr(P), o[8], o[5], B, ptr(self.asave[t]),
-                                 ctypes.c_void_p(self.acts.data_ptr() + 4 * t * B * N), ptr(self.dqa[t]), ptr(dn),
-                                 ptr(self.dh), ptr(self.dgi[t]), ptr(self.dgh[t]), ptr(self.dqv[t]), s), "agent bwd")
-        if split and not pair_bwd:
-            torch.cuda.current_stream(self.dev).wait_stream(side)   # join: the mixer deltas are complete
-        # ---- deferred weight gradients: batched over all C*B rows, grouped by agent; every
-        # outer product of the update (agent + mixer) in ONE split-M launch (+ its partial sum)
-        jobs = []
-        self._agent_wgrad(L, s, obs_p, reset_p, CB, jobs)
-        mjobs = []
-        if self.has_mixer:
-            self._mixer_wgrad(L, s, obs_p, reset_p, CB, mjobs)
+            check(L.mm_agent_bwd_seq(*aseq, s), "agent bwd seq")
+        else:
+            for t in range(C - 1, -1, -1):
+                dn = self.ones_f if t == C - 1 else self.done[t * B:(t + 1) * B]
+                if self.has_mixer and not plan.seq:
+                    check(L.mm_mixer_bwd(B, N, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.msave[t]),
+                                         ptr(self.qa[t]), ptr(self.dq[t]), ptr(dn), ptr(self.dhm), ptr(self.dqa[t]),
+                                         ptr(self.mdelta[t]), s), "mixer bwd")
+                check(L.mm_agent_bwd(dims, ptr(P), o[8], o[5], B, ptr(self.asave[t]),
+                                     ctypes.c_void_p(self.acts.data_ptr() + 4 * t * B * N), ptr(self.dqa[t]),
+                                     ptr(dn), ptr(self.dh), ptr(self.dgi[t]), ptr(self.dgh[t]), ptr(self.dqv[t]), s),
+                      "agent bwd")
+        if fork_rec:
+            cur.wait_stream(self._side_stream())   # join: the mixer deltas are complete
+
+    # ---- deferred weight gradients: batched over all C*B rows, grouped by agent; every outer product of the
+    # update (agent + mixer) in ONE split-M launch (+ its partial sum)
+    def _weight_grads(self, L, s, obs_p, reset_p):
+        CB = self.C * self.B
+        self._agent_dgrad(L, s, CB)
+        jobs = self._agent_wgrad_jobs(obs_p, reset_p, CB)
+        mjobs = self._mixer_wgrad_jobs(obs_p, reset_p, CB) if self.has_mixer else []
+        part, npart = ptr(self._opart), self._opart.numel()
+        if not self.mixer_bf3:
+            jobs += mjobs
+        arr = (OuterArgs * len(jobs))(*jobs)
+        check(L.mm_outer_reduce_batch(arr, len(jobs), part, npart, s), "outer batch")
         if self.mixer_bf3:
             # fast mode at large batches: the agent weight gradients stay exact f32 (the fp32 parity bar); only
             # the MIXER's products run as bf16x3 splits (~2^-16 relative), a second launch over the same partials
-            arr = (OuterArgs * len(jobs))(*jobs)
-            check(L.mm_outer_reduce_batch(arr, len(jobs), ptr(self._opart), self._opart.numel(), s), "outer batch")
             marr = (OuterArgs * len(mjobs))(*mjobs)
-            check(L.mm_outer_reduce_batch_bf3(marr, len(mjobs), ptr(self._opart), self._opart.numel(), s),
-                  "outer batch (mixer, bf16x3)")
-            return
-        jobs += mjobs
-        arr = (OuterArgs * len(jobs))(*jobs)
-        check(L.mm_outer_reduce_batch(arr, len(jobs), ptr(self._opart), self._opart.numel(), s), "outer batch")
+            check(L.mm_outer_reduce_batch_bf3(marr, len(mjobs), part, npart, s), "outer batch (mixer, bf16x3)")
 
     @property
     def mixer_bf3(self):
@@ -515,93 +616,6 @@ class QLearner:
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(self.dev)
         return self._side
-
-    def _fwd_pair(self):
-        """Both paired forward launches apply (QMIX, exact-f32 state projection, the B = 32 shapes)."""
-        if self._pair_ok is None:
-            mx = self.mix
-            self._pair_ok = bool(self._pair_fwd and self.has_mixer and not self.double and not self.mixer_fp16 and
-                                 lib().mm_agent_mixer_pair_supported(ctypes.byref(self.beh.dims), self.B, self.C,
-                                                                     self.N, mx.S, mx.Hm, mx.K1) == 3)
-        return self._pair_ok
-
-    def _mixer_split(self):
-        """The mixer's state projection + GRU recurrence run on a second stream beside the agent chain (and its
-        recurrence backward beside the agent BPTT): sequence path, both split mixer kernels available."""
-        if not (self.has_mixer and self.seq and self.B < 512):
-            return False
-        mx = self.mix
-        return bool(lib().mm_mixer_seq_split(self.B, self.N, mx.S, mx.Hm, mx.K1, ptr(mx.flat), ptr(self.mxws),
-                                             self.C))
-
-    def _mixer_nets(self):
-        nets = (MixNetIO * 2)()
-        for k, (Pm, q, qt, sv, gi) in enumerate(((self.mix.flat, self.qa, self.qtot, self.msave, self.gi_b),
-                                                  (self.tmix.flat, self.maxq, self.qtot_t, None, self.gi_t))):
-            n = nets[k]
-            n.P, n.q, n.gi, n.qtot = Pm.data_ptr(), q.data_ptr(), gi.data_ptr(), qt.data_ptr()
-            n.s_off = self.s_off.data_ptr()
-            n.h_in, n.h_out = self.hm[0].data_ptr(), self.mhseq[k].data_ptr()
-            n.reset = self.ones8.data_ptr()
-            n.save = sv.data_ptr() if sv is not None else None
-        return nets
-
-    def _mixer_seq_call(self, L, fn, s, what):
-        mx = self.mix
-        check(fn(self.B, self.N, mx.S, mx.Hm, mx.K1, self._mixer_nets(), 2, self.C, ptr(self.done8), s), what)
-
-    def _forward_seq(self, L, s, obs_p, reset_p, split=False, join=False, pair=False):
-        """REC of both nets over all C steps in one chunk-sequence launch, then the mixers per step."""
-        B, C, N, H = self.B, self.C, self.N, self.H
-        ib, it = QFwdIO(), QFwdIO()
-        for io, gi in ((ib, self.gi_ab), (it, self.gi_at)):
-            io.obs = obs_p.value
-            io.gi = gi.data_ptr()
-        ib.mode = MM_Q_GATHER
-        ib.act_in, ib.act_se = self.acts.data_ptr(), N
-        ib.qsel_out = self.qa.data_ptr()
-        ib.save = self.asave.data_ptr()
-        it.mode = MM_Q_MAX
-        it.qsel_out = self.maxq.data_ptr()
-        if pair:
-            # + the mixers' GRU over the state (mm_mixer_fwd_seq_rec) in the same grid, then the hypernet pass
-            mx = self.mix
-            check(L.mm_agent_mixer_rec_seq(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(ib),
-                                           ptr(self.tgt.packed), ctypes.byref(it), B, C, ptr(self.done8), N, mx.S,
-                                           mx.Hm, mx.K1, self._mixer_nets(), 2, ptr(self.done8), s),
-                  "rec seq + mixer recurrence")
-            self._mixer_seq_call(L, L.mm_mixer_fwd_seq_hyper, s, "mixer fwd seq (hypernets)")
-            return
-        check(L.mm_agent_q_rec_seq2(ctypes.byref(self.beh.dims), ptr(self.beh.packed), ctypes.byref(ib), B,
-                                    ptr(self.tgt.packed), ctypes.byref(it), B, C, ptr(self.done8), s), "rec seq")
-        if self.has_mixer:
-            mx = self.mix
-            if split:
-                # join the mixer recurrence (side stream), then the hypernet pass over the agents' Q
-                if join:
-                    torch.cuda.current_stream(self.dev).wait_stream(self._side_stream())
-                self._mixer_seq_call(L, L.mm_mixer_fwd_seq_hyper, s, "mixer fwd seq (hypernets)")
-                return
-            if L.mm_mixer_fwd_seq_fits(B, N, mx.Hm, mx.K1):
-                # all C steps of both mixers in ONE launch: weights staged once into LDS, the mixer
-                # hidden carried in LDS (bit-identical to the per-step launches below)
-                self._mixer_seq_call(L, L.mm_mixer_fwd_seq, s, "mixer fwd seq")
-                return
-            # per-step mixer launches (B >= 512: 8 samples per block share the weight reads), reading
-            # the REC outputs of every step
-            for t in range(C):
-                nets = (MixNetIO * 2)()
-                for k, (Pm, q, off, h, qt, sv, gi) in enumerate(
-                        ((self.mix.flat, self.qa[t], self.s_off, self.hm, self.qtot[t], self.msave[t], self.gi_b[t]),
-                         (self.tmix.flat, self.maxq[t], self.s2_off, self.hmt, self.qtot_t[t], None, self.gi_t[t]))):
-                    n = nets[k]
-                    n.P, n.q, n.gi = Pm.data_ptr(), q.data_ptr(), gi.data_ptr()
-                    n.s_off = off.data_ptr() + 8 * t * B
-                    n.h_in, n.h_out = h[t % 2].data_ptr(), h[(t + 1) % 2].data_ptr()
-                    n.reset = self.ones8.data_ptr() if t == 0 else self.done8.data_ptr() + (t - 1) * B
-                    n.qtot = qt.data_ptr()
-                    n.save = sv.data_ptr() if sv is not None else None
-                check(L.mm_mixer_fwd(B, N, mx.S, mx.Hm, mx.K1, obs_p, reset_p, nets, 2, s), "mixer fwd")
 
     def apply_grads(self, grad_scale=1.0, per=None, sample_next=None):
         """clip_grad_norm_ + Adam (grads scaled first, e.g. 1/world after an all-reduce), then repack
@@ -641,10 +655,6 @@ class QLearner:
         self.updates += 1
         return False
 
-    def _uses_h3(self):
-        """Whether this learner's own forward reads the fp16x3 image (the opt-in fast PRE)."""
-        return self.mixer_fp16 and self.C * self.B >= 2048 and self.fast_pre
-
     def _pack(self, net, s=None):
         """Repack what the learner's forward reads: the exact-f32 image only, unless the fast PRE runs (the
         rollout's fp16x3 image is then refreshed lazily by its own full pack before the next rollout step)."""
@@ -657,58 +667,47 @@ class QLearner:
         self.compute_grads(obs_base, reset_obs_ptr)
         self.apply_grads()
 
-    def _outer(self, L, s, U, u_g, u_m, V, v_g, v_m, dW, w_g, db, b_g, M, R, Cc, groups, v_off=None, v_reset=None,
-               jobs=None):
-        a = OuterArgs()
-        a.U, a.u_g, a.u_m = U, u_g, u_m
-        a.V, a.v_g, a.v_m = V, v_g, v_m
-        a.v_off = v_off
-        a.v_reset = v_reset
-        a.dW, a.w_g = dW, w_g
-        a.db, a.b_g = db, b_g
-        a.M, a.R, a.Cc, a.accumulate, a.groups = M, R, Cc, 0, groups
-        if jobs is not None:
-            jobs.append(a)
-        else:
-            check(L.mm_outer_reduce(ctypes.byref(a), s), "outer_reduce")
+    @staticmethod
+    def _outer(U, u_g, u_m, V, v_g, v_m, dW, w_g, db, b_g, M, R, Cc, groups, v_off=None, v_reset=None):
+        """One job of the batched outer reduce (mm_outer_reduce_batch; the fields in mm_outer_args order)."""
+        return OuterArgs(U, u_g, u_m, V, v_g, v_m, v_off, v_reset, dW, w_g, db, b_g, M, R, Cc, 0, groups)
 
-    def _tmv(self, L, s, W, w_g, X, x_g, x_m, Z, z_g, z_m, Y, y_g, y_m, M, R, Cc, groups):
-        a = TmvArgs()
-        a.W, a.w_g, a.X, a.x_g, a.x_m, a.Z, a.z_g, a.z_m, a.Y, a.y_g, a.y_m = W, w_g, X, x_g, x_m, Z, z_g, z_m, Y, y_g, y_m
-        a.M, a.R, a.Cc, a.groups = M, R, Cc, groups
-        check(L.mm_tmv(ctypes.byref(a), s), "tmv")
+    def _agent_dgrad(self, L, s, M):
+        """Data gradients of the agent's feed-forward layers (the weight-gradient jobs only read them):
+        dpre2 = (x2 > 0) * Wih^T dgi ; dpre1 = (x1 > 0) * W2^T dpre2."""
+        N, F1, G, H, SD, o = self.N, self.F1, self.G, self.H, self.SD, self.beh.offs
+        pp, sv, f = self.P.data_ptr(), self.asave.data_ptr(), 4
+        for a in (TmvArgs(pp + f * o[4], 3 * H * G, self.dgi.data_ptr(), 3 * H, N * 3 * H, sv + f * F1, SD, N * SD,
+                          self.dpre2.data_ptr(), G, N * G, M, 3 * H, G, N),
+                  TmvArgs(pp + f * o[2], G * F1, self.dpre2.data_ptr(), G, N * G, sv, SD, N * SD,
+                          self.dpre1.data_ptr(), F1, N * F1, M, G, F1, N)):     # (fields in mm_tmv_args order)
+            check(L.mm_tmv(ctypes.byref(a), s), "tmv")
 
-    def _agent_wgrad(self, L, s, obs_p, reset_p, M, jobs):
+    def _agent_wgrad_jobs(self, obs_p, reset_p, M):
         N, D, F1, G, H, A, SD = self.N, self.D, self.F1, self.G, self.H, self.A, self.SD
         o = self.beh.offs          # W1 b1 W2 b2 Wih Whh bih bhh Wq bq
-        gp, pp = self.Gr.data_ptr(), self.P.data_ptr()
+        gp = self.Gr.data_ptr()
         sv = self.asave.data_ptr()
         f = 4
-        # data gradients of the feed-forward layers first (the outer products below only read them)
-        # dpre2 = (x2 > 0) * Wih^T dgi ; dpre1 = (x1 > 0) * W2^T dpre2
-        if L is not None:
-            self._tmv(L, s, pp + f * o[4], 3 * H * G, self.dgi.data_ptr(), 3 * H, N * 3 * H, sv + f * F1, SD,
-                      N * SD, self.dpre2.data_ptr(), G, N * G, M, 3 * H, G, N)
-            self._tmv(L, s, pp + f * o[2], G * F1, self.dpre2.data_ptr(), G, N * G, sv, SD, N * SD,
-                      self.dpre1.data_ptr(), F1, N * F1, M, G, F1, N)
-        # Wq, bq <- dq (one-hot) x h_out
-        self._outer(L, s, self.dqv.data_ptr(), A, N * A, sv + f * (F1 + G + 5 * H), SD, N * SD,
-                    gp + f * o[8], A * H, gp + f * o[9], A, M, A, H, N, jobs=jobs)
-        # Whh, bhh <- dgh x h_in
-        self._outer(L, s, self.dgh.data_ptr(), 3 * H, N * 3 * H, sv + f * (F1 + G), SD, N * SD,
-                    gp + f * o[5], 3 * H * H, gp + f * o[7], 3 * H, M, 3 * H, H, N, jobs=jobs)
-        # Wih, bih <- dgi x x2
-        self._outer(L, s, self.dgi.data_ptr(), 3 * H, N * 3 * H, sv + f * F1, SD, N * SD,
-                    gp + f * o[4], 3 * H * G, gp + f * o[6], 3 * H, M, 3 * H, G, N, jobs=jobs)
-        # W2, b2 <- dpre2 x x1
-        self._outer(L, s, self.dpre2.data_ptr(), G, N * G, sv, SD, N * SD,
-                    gp + f * o[2], G * F1, gp + f * o[3], G, M, G, F1, N, jobs=jobs)
-        # W1, b1 <- dpre1 x obs (gathered through the s_t offsets)
-        self._outer(L, s, self.dpre1.data_ptr(), F1, N * F1, obs_p.value, D, 0,
-                    gp + f * o[0], F1 * D, gp + f * o[1], F1, M, F1, D, N,
-                    v_off=self.s_off.data_ptr(), v_reset=reset_p.value, jobs=jobs)
+        return [
+            # Wq, bq <- dq (one-hot) x h_out
+            self._outer(self.dqv.data_ptr(), A, N * A, sv + f * (F1 + G + 5 * H), SD, N * SD,
+                        gp + f * o[8], A * H, gp + f * o[9], A, M, A, H, N),
+            # Whh, bhh <- dgh x h_in
+            self._outer(self.dgh.data_ptr(), 3 * H, N * 3 * H, sv + f * (F1 + G), SD, N * SD,
+                        gp + f * o[5], 3 * H * H, gp + f * o[7], 3 * H, M, 3 * H, H, N),
+            # Wih, bih <- dgi x x2
+            self._outer(self.dgi.data_ptr(), 3 * H, N * 3 * H, sv + f * F1, SD, N * SD,
+                        gp + f * o[4], 3 * H * G, gp + f * o[6], 3 * H, M, 3 * H, G, N),
+            # W2, b2 <- dpre2 x x1
+            self._outer(self.dpre2.data_ptr(), G, N * G, sv, SD, N * SD,
+                        gp + f * o[2], G * F1, gp + f * o[3], G, M, G, F1, N),
+            # W1, b1 <- dpre1 x obs (gathered through the s_t offsets)
+            self._outer(self.dpre1.data_ptr(), F1, N * F1, obs_p.value, D, 0,
+                        gp + f * o[0], F1 * D, gp + f * o[1], F1, M, F1, D, N,
+                        v_off=self.s_off.data_ptr(), v_reset=reset_p.value)]
 
-    def _mixer_wgrad(self, L, s, obs_p, reset_p, M, jobs):
+    def _mixer_wgrad_jobs(self, obs_p, reset_p, M):
         mx = self.mix
         Hm, K1, N, S = mx.Hm, mx.K1, self.N, mx.S
         MSD, MDD = self.MSD, self.MDD
@@ -717,20 +716,20 @@ class QLearner:
         dl, sv = self.mdelta.data_ptr(), self.msave.data_ptr()
         f = 4
         hm1 = sv + f * 5 * Hm
-        # GRU input weights <- dgi x state (gathered), recurrent <- dgh x hm0
-        self._outer(L, s, dl, 0, MDD, obs_p.value, 0, 0, mo["gWih"], 0, mo["gbih"], 0, M, 3 * Hm, S, 1,
-                    v_off=self.s_off.data_ptr(), v_reset=reset_p.value, jobs=jobs)
-        self._outer(L, s, dl + f * 3 * Hm, 0, MDD, sv, 0, MSD, mo["gWhh"], 0, mo["gbhh"], 0, M, 3 * Hm, Hm, 1, jobs=jobs)
-        # hypernetworks <- deltas x hm1
-        self._outer(L, s, dl + f * 6 * Hm, 0, MDD, hm1, 0, MSD, mo["w1W"], 0, mo["w1b"], 0, M, N * K1, Hm, 1, jobs=jobs)
-        self._outer(L, s, dl + f * (6 * Hm + N * K1), 0, MDD, hm1, 0, MSD, mo["b1W"], 0, mo["b1b"], 0, M, K1, Hm, 1, jobs=jobs)
-        self._outer(L, s, dl + f * (6 * Hm + N * K1 + K1), 0, MDD, hm1, 0, MSD, mo["w2W"], 0, mo["w2b"], 0, M, K1,
-                    Hm, 1, jobs=jobs)
-        self._outer(L, s, dl + f * (6 * Hm + N * K1 + 2 * K1), 0, MDD, hm1, 0, MSD, mo["b2aW"], 0, mo["b2ab"], 0, M,
-                    K1, Hm, 1, jobs=jobs)
-        # final b2 layer <- dQ x relu(b2 hidden)
-        self._outer(L, s, dl + f * (6 * Hm + N * K1 + 3 * K1), 0, MDD, sv + f * (6 * Hm + N * K1 + 2 * K1), 0, MSD,
-                    mo["b2bW"], 0, mo["b2bb"], 0, M, 1, K1, 1, jobs=jobs)
+        hy = 6 * Hm + N * K1      # the deltas / saves after the GRU's and w1's
+        return [
+            # GRU input weights <- dgi x state (gathered), recurrent <- dgh x hm0
+            self._outer(dl, 0, MDD, obs_p.value, 0, 0, mo["gWih"], 0, mo["gbih"], 0, M, 3 * Hm, S, 1,
+                        v_off=self.s_off.data_ptr(), v_reset=reset_p.value),
+            self._outer(dl + f * 3 * Hm, 0, MDD, sv, 0, MSD, mo["gWhh"], 0, mo["gbhh"], 0, M, 3 * Hm, Hm, 1),
+            # hypernetworks <- deltas x hm1
+            self._outer(dl + f * 6 * Hm, 0, MDD, hm1, 0, MSD, mo["w1W"], 0, mo["w1b"], 0, M, N * K1, Hm, 1),
+            self._outer(dl + f * hy, 0, MDD, hm1, 0, MSD, mo["b1W"], 0, mo["b1b"], 0, M, K1, Hm, 1),
+            self._outer(dl + f * (hy + K1), 0, MDD, hm1, 0, MSD, mo["w2W"], 0, mo["w2b"], 0, M, K1, Hm, 1),
+            self._outer(dl + f * (hy + 2 * K1), 0, MDD, hm1, 0, MSD, mo["b2aW"], 0, mo["b2ab"], 0, M, K1, Hm, 1),
+            # final b2 layer <- dQ x relu(b2 hidden)
+            self._outer(dl + f * (hy + 3 * K1), 0, MDD, sv + f * (hy + 2 * K1), 0, MSD, mo["b2bW"], 0, mo["b2bb"], 0,
+                        M, 1, K1, 1)]
 
     # ------------------------------------------------------------------ full update from the PER
     def sample_and_grads(self, per, store, reset_obs_ptr, fracs=None, seed=0, counter=0, presampled=False):
@@ -801,40 +800,40 @@ class QLearner:
         self._push_double_eps()
         torch.cuda.synchronize(self.dev)
         n0 = self.updates
-        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with graph_capture(g1):
+
+        def grads(presampled=False):
             if per is None:          # the batch loaded by load_batch (tests, reference-shaped callers)
                 self.compute_grads(self._obs_ptr, self._reset_obs)
             else:
-                self.sample_and_grads(per, store, reset_obs_ptr, seed=seed)
-        with graph_capture(g2):
+                self.sample_and_grads(per, store, reset_obs_ptr, seed=seed, presampled=presampled)
+
+        def step(sample_next=None):     # True: the step launch also drew the next update's batch
             if per is None:
                 self.apply_grads(self._graph_scale)
-            else:
-                self.apply_and_reprioritize(per, self._graph_scale)
+                return False
+            return self.apply_and_reprioritize(per, self._graph_scale, sample_next=sample_next)
+
+        def update(presampled=False, sample_next=None):
+            grads(presampled)
+            return step(sample_next)
+
+        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with graph_capture(g1):
+            grads()
+        with graph_capture(g2):
+            step()
         # single-replica updates replay ONE graph holding both parts (one graph launch per update
         # instead of two: the B = 32 update is launch-latency bound)
         g12 = torch.cuda.CUDAGraph()
         with graph_capture(g12):
-            if per is None:
-                self.compute_grads(self._obs_ptr, self._reset_obs)
-                self.apply_grads(self._graph_scale)
-            else:
-                self.sample_and_grads(per, store, reset_obs_ptr, seed=seed)
-                self.apply_and_reprioritize(per, self._graph_scale)
+            update()
         self.graph_multi, self._per_replay = None, int(per_replay)
         if self._per_replay > 1:
             gk = torch.cuda.CUDAGraph()
             with graph_capture(gk):
                 ahead = False   # each update's step launch also draws the next update's batch
                 for i in range(self._per_replay):
-                    if per is None:
-                        self.compute_grads(self._obs_ptr, self._reset_obs)
-                        self.apply_grads(self._graph_scale)
-                    else:
-                        self.sample_and_grads(per, store, reset_obs_ptr, seed=seed, presampled=ahead)
-                        ahead = self.apply_and_reprioritize(per, self._graph_scale,
-                                                            sample_next=(seed, 0) if i + 1 < self._per_replay else None)
+                    ahead = update(presampled=ahead, sample_next=(seed, 0) if i + 1 < self._per_replay else None)
             self.graph_multi = gk
         self.updates = n0
         self.graphs = (g1, g2)
