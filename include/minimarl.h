@@ -727,7 +727,7 @@ int mm_mappo_insert(const uint8_t* done, int32_t n_agents, int32_t hidden, int64
  * Batch = PrioritizedRecReplayBuffer.sample layout (rec_buffer.py:192-240): obs [N, T+1, B, D],
  * share_obs [T+1, B, S], acts one-hot [N, T, B, A], rewards [N, T, B] (agent 0's are used,
  * qmix.py:169), dones_env [T, B], is_weight [B] (NULL: no PER). Supported: H = 64, A = 5,
- * D in {47, 94}; QMIX: hypernet_layers = 2, any S, mixer_hidden K <= MM_OFFQ_MAX_MIXER_HIDDEN (the
+ * D in {3, 47, 94} (3: Switch with local observations and the clock); QMIX: hypernet_layers = 2, any S, mixer_hidden K <= MM_OFFQ_MAX_MIXER_HIDDEN (the
  * mixer kernels give one lane of a 64-lane wave to each mixing unit), N*K <= 4096. For a larger K
  * mm_offq_param_counts, mm_offq_mixer_offsets and mm_offq_loss_grad return MM_EINVAL and
  * mm_offq_workspace_bytes returns -1. */
@@ -827,6 +827,18 @@ int mm_switch_step_rows_td(mm_switch* w, const int32_t* act, float* next_obs, in
                            const int32_t* td_act, float* chunk_td, int32_t step_in_chunk, int32_t chunk_len,
                            uint8_t* store_act, float* store_rew, uint8_t* store_done, const int64_t* td_rows,
                            uint64_t* counter, mm_stream_t s);
+/* mm_offq_collect for E lockstep Switch envs: the same loop, RNG stream, outputs and io contract, one launch per
+ * T-step episode, every env from reset (the handle supplies n_agents, max_steps and step_cost; its live state is
+ * neither read nor written). obs is [T+1, E, N, 3] = [row feature, column feature, step / max_steps]. The env is
+ * stepped while not all agents are done; dones [T, E, N, 1] holds each agent's own done flag (1 from the step it
+ * reaches its target, and for every agent at max_steps), dones_env [T, E, 1] their conjunction. An agent's reward
+ * is +5 on the step it reaches its target and step_cost otherwise, also after it is done, while the env runs; 0
+ * once the env is done. Supported (mm_offq_collect_switch_supported returns 1; otherwise the launch returns
+ * MM_EINVAL and mm_last_error says why): local observations with the clock (D = 3), H = 64, A = 5,
+ * dims.n_agents = the env's agents (2..4), E in [1, 2^24], T in [1, 65536]. */
+int mm_offq_collect_switch_supported(const mm_switch* env, const mm_offq_dims* d, int64_t n_envs, int32_t T);
+int mm_offq_collect_switch(mm_switch* env, const mm_offq_dims* d, const float* P, const mm_offq_collect_io* io,
+                           int64_t n_envs, int32_t T, mm_stream_t s);
 
 /* ------------------------------------------------------- offpolicy episode replay (mm_erb_*) */
 /* RecReplayBuffer / PrioritizedRecReplayBuffer of one policy (offpolicy/utils/rec_buffer.py:10-324)

@@ -1446,6 +1446,10 @@ struct OffqShape {
 
 #define MM_OFFQ_DISPATCH(d, CALL)                                                                  \
   do {                                                                                             \
+    if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == 3) {                           \
+      using SH = mm::OffqShape<3, 64, 5>;                                                           \
+      return CALL;                                                                                 \
+    }                                                                                              \
     if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == 47) {                          \
       using SH = mm::OffqShape<47, 64, 5>;                                                          \
       return CALL;                                                                                 \
@@ -1454,7 +1458,7 @@ struct OffqShape {
       using SH = mm::OffqShape<94, 64, 5>;                                                          \
       return CALL;                                                                                 \
     }                                                                                              \
-    mm::set_error("offq: unsupported dims D=%d H=%d A=%d (supported: D 47|94, H 64, A 5)", (d)->obs_dim, \
+    mm::set_error("offq: unsupported dims D=%d H=%d A=%d (supported: D 3|47|94, H 64, A 5)", (d)->obs_dim, \
                   (d)->hidden, (d)->n_actions);                                                    \
     return MM_EINVAL;                                                                              \
   } while (0)
@@ -1497,6 +1501,7 @@ int mm_offq_mixer_offsets(const mm_offq_dims* d, int64_t offs[15]) {
 
 int64_t mm_offq_workspace_bytes(const mm_offq_dims* d, int32_t T, int32_t B) {
   if (mm::check_dims(d) || T < 1 || B < 1) return -1;
+  if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 3) return mm::OffqShape<3, 64, 5>::layout(d, T, B).total * 4;
   if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 47) return mm::OffqShape<47, 64, 5>::layout(d, T, B).total * 4;
   if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 94) return mm::OffqShape<94, 64, 5>::layout(d, T, B).total * 4;
   return -1;
@@ -1520,7 +1525,7 @@ int mm_offq_loss_grad(const mm_offq_dims* d, const mm_offq_batch* b, const float
 
 int64_t mm_offq_qvals_workspace_bytes(const mm_offq_dims* d, int32_t L, int64_t R) {
   if (!d || L < 1 || R < 1 || d->hidden != 64) return -1;
-  return mm::OffqShape<47, 64, 5>::qvals_ws(L, R) * 4;
+  return mm::OffqShape<47, 64, 5>::qvals_ws(L, R) * 4;   // gi and hs only: the same for every obs_dim
 }
 
 int mm_offq_q_values(const mm_offq_dims* d, const float* P, const float* obs, const float* h0, float* q, float* h_out,

@@ -10,32 +10,15 @@
 
 #include "common.h"
 #include "minimarl.h"
+#include "switch_dev.h"
 
 namespace mm {
-
-struct SwitchState {
-  int8_t pos[4][2];
-  uint8_t adone[4];
-  int32_t steps;
-};
-
-// obs feature tables round(c / 6, 2), round(r / 2, 2) (Python floats -> float32), passed by value in
-// the kernel arguments (no per-device constant-memory state to initialise)
-struct SwitchTab {
-  float col[7];
-  float row[3];
-};
 
 static SwitchTab switch_tables() {
   SwitchTab t;
   for (int c = 0; c < 7; ++c) t.col[c] = (float)(std::round(c / 6.0 * 100.0) / 100.0);
   for (int r = 0; r < 3; ++r) t.row[r] = (float)(r / 2.0);
   return t;
-}
-
-// open cells of the 3 x 7 grid: the middle row and columns 0, 1, 5, 6
-__device__ __forceinline__ bool sw_open(int r, int c) {
-  return r >= 0 && r < 3 && c >= 0 && c < 7 && (r == 1 || c <= 1 || c >= 5);
 }
 
 __device__ __forceinline__ void sw_init(SwitchState& s, int N) {
@@ -247,14 +230,6 @@ __global__ __launch_bounds__(256) void switch_step_kernel(SwitchTab tab, SwitchS
 }
 
 }  // namespace mm
-
-struct mm_switch {
-  mm_switch_cfg cfg;
-  mm::SwitchTab tab;
-  int64_t E;
-  mm::SwitchState* st;
-  float* reset_obs;   // [N, D] the (deterministic) reset obs
-};
 
 namespace mm {
 static int switch_step(mm_switch* w, const int32_t* act, float* next_obs, int64_t next_se, const int64_t* next_row,

@@ -386,6 +386,8 @@ class OffqCollectIO(ctypes.Structure):
 _SIGS += [
     ("mm_offq_collect_supported", c_i32, [c_vp, _OD, c_i64, c_i32]),
     ("mm_offq_collect", c_i32, [c_vp, _OD, c_vp, ctypes.POINTER(OffqCollectIO), c_i64, c_i32, c_vp]),
+    ("mm_offq_collect_switch_supported", c_i32, [c_vp, _OD, c_i64, c_i32]),
+    ("mm_offq_collect_switch", c_i32, [c_vp, _OD, c_vp, ctypes.POINTER(OffqCollectIO), c_i64, c_i32, c_vp]),
 ]
 
 

@@ -151,6 +151,7 @@ class OffQTrainConfig:
     train_interval_episode: int = 1
     num_env_steps: int = 2000000
     seed: int = 1
+    env: str = "checkers"               # "checkers" | "switch" (local observations with the clock, 2..4 agents)
 
 
 @dataclass

@@ -1,9 +1,9 @@
 """Offpolicy QMix / VDN end to end on the MI355X: the device episode collector and the training runner.
 
 ``OffQCollector`` stands in for ``collect_rollout`` (offpolicy/runner/shared/magym_runner.py:40-141): one
-``mm_offq_collect`` launch (csrc/offq_collect.hip) runs a whole T-step episode of E lockstep Checkers envs with
-the behavior agent net and per-(env, agent) epsilon-greedy, and leaves the episode fields in HBM in the replay
-buffer's insert layout. ``OffQRunner`` is ``RecRunner.run`` / ``warmup`` / ``batch_train_q``
+``mm_offq_collect`` / ``mm_offq_collect_switch`` launch (csrc/offq_collect.hip) runs a whole T-step episode of E
+lockstep Checkers or Switch envs with the behavior agent net and per-(env, agent) epsilon-greedy, and leaves the
+episode fields in HBM in the replay buffer's insert layout. ``OffQRunner`` is ``RecRunner.run`` / ``warmup`` / ``batch_train_q``
 (runner/shared/base_runner.py:193-298) over it, ``RecReplayBuffer.insert_collected`` and ``OffQMix``.
 
 Deviations from the reference:
@@ -23,7 +23,7 @@ import torch
 
 from ._lib import OffqCollectIO, check, lib
 from .config import OffQTrainConfig
-from .env import VecEnv
+from .env import SwitchVecEnv, make_env
 from .offq import OffQMix
 from .qnet import ptr, stream_handle
 from .recbuf import PrioritizedRecReplayBuffer, RecReplayBuffer
@@ -41,8 +41,10 @@ class DecayThenFlatSchedule:
 
 
 class OffQCollector:
-    """One-launch episode collection for ``env`` (a Checkers ``VecEnv`` with local observations) and ``policy``
-    (an ``OffQMix``: its behavior parameters ``policy.P`` are read in place, so updates show in the next collect).
+    """One-launch episode collection for ``env`` (a Checkers ``VecEnv`` with local observations, or a
+    ``SwitchVecEnv`` with local observations and the clock) and ``policy`` (an ``OffQMix``: its behavior parameters
+    ``policy.P`` are read in place, so updates show in the next collect). On Switch ``dones`` holds each agent's
+    own done flag and differs from ``dones_env``.
     The env handle supplies the rules and the reset state; its live state is neither read nor written.
     Buffers are allocated once and overwritten by every ``collect``; the launch does not sync and reads epsilon
     and the RNG step counter from device memory, so a captured ``launch()`` replays with whatever ``set_epsilon``
@@ -55,10 +57,14 @@ class OffQCollector:
         self.device = policy.device
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.common_reward = bool(common_reward)
-        if not lib().mm_offq_collect_supported(env.handle(), ctypes.byref(policy.dims), self.E, self.T):
+        if isinstance(env, SwitchVecEnv):
+            self._name, supported = "offq_collect_switch", lib().mm_offq_collect_switch_supported
+        else:
+            self._name, supported = "offq_collect", lib().mm_offq_collect_supported
+        self._collect = getattr(lib(), "mm_" + self._name)
+        if not supported(env.handle(), ctypes.byref(policy.dims), self.E, self.T):
             # the launch reports why
-            check(lib().mm_offq_collect(env.handle(), ctypes.byref(policy.dims), None, None, self.E, self.T, None),
-                  "offq_collect")
+            check(self._collect(env.handle(), ctypes.byref(policy.dims), None, None, self.E, self.T, None), self._name)
         dev, E, N, T_ = self.device, self.E, self.N, self.T
         self.fields = {"obs": torch.zeros(T_ + 1, E, N, self.D, device=dev),
                        "acts": torch.zeros(T_, E, N, self.A, device=dev),
@@ -88,8 +94,8 @@ class OffQCollector:
 
     def launch(self):
         """The collect launch and the counter advance (+T), nothing else: capturable in a HIP graph."""
-        check(lib().mm_offq_collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(self.policy.P),
-                                    ctypes.byref(self._io), self.E, self.T, stream_handle(self.device)), "offq_collect")
+        check(self._collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(self.policy.P),
+                            ctypes.byref(self._io), self.E, self.T, stream_handle(self.device)), self._name)
         self.counter.add_(self.T)
 
     def collect(self, eps):
@@ -102,8 +108,8 @@ class OffQCollector:
 
 
 class OffQRunner:
-    """``RecRunner`` for qmix / vdn on Checkers (base_runner.py:193-298): ``warmup()`` then ``run()`` per iteration.
-    Per collect of E = ``n_envs`` episodes the counters advance as the reference's do with ``num_envs``:
+    """``RecRunner`` for qmix / vdn on Checkers or Switch (``cfg.env``; base_runner.py:193-298): ``warmup()`` then
+    ``run()`` per iteration. Per collect of E = ``n_envs`` episodes the counters advance as the reference's do with ``num_envs``:
     ``total_env_steps`` by E per step (T E per collect), ``num_episodes_collected`` by E; ``total_train_steps`` by
     one per gradient update."""
 
@@ -114,7 +120,7 @@ class OffQRunner:
         self.device = torch.device(device)
         E, N, T = cfg.n_envs, cfg.n_agents, cfg.episode_length
         self.num_envs, self.num_agents, self.episode_length = E, N, T
-        self.env = VecEnv(E, N, max_steps=T, step_cost=cfg.step_cost, full_observable=False, device=device)
+        self.env = make_env(cfg.env, E, N, max_steps=T, step_cost=cfg.step_cost, full_observable=False, device=device)
         D, A = self.env.obs_dim, self.env.n_actions
         self.trainer = OffQMix(N, D, A, T, cfg.batch_size, mixer=cfg.algorithm_name, hidden=cfg.hidden_size,
                                mixer_hidden=cfg.mixer_hidden_dim, hyper_hidden=cfg.hypernet_hidden_dim,
