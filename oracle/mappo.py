@@ -242,7 +242,7 @@ def adam(P, G, state, lr, eps, betas=(0.9, 0.999)):
 
 
 def ppo_train(PA, PC, data, vn, epochs, L, perms=None, lr=1e-4, eps=1e-5, max_norm=0.5,
-              value_loss_coef=0.5, entropy_coef=0.01, record=None):
+              value_loss_coef=0.5, entropy_coef=0.01, record=None, clip=0.2, huber_delta=10.0):
     """R_MAPPO.train with one minibatch per epoch (train_batch_size 1). Returns new PA, PC, vn."""
     adv = normalized_advantages(data, vn)
     sa, sc = {}, {}
@@ -251,7 +251,8 @@ def ppo_train(PA, PC, data, vn, epochs, L, perms=None, lr=1e-4, eps=1e-5, max_no
         pa = {k: v.detach().clone().requires_grad_(True) for k, v in PA.items()}
         pc = {k: v.detach().clone().requires_grad_(True) for k, v in PC.items()}
         vn.update(b["returns"])
-        pol, ent, vloss, ratio = ppo_losses(pa, pc, b, L, vn, entropy_coef=entropy_coef)
+        pol, ent, vloss, ratio = ppo_losses(pa, pc, b, L, vn, clip=clip, huber_delta=huber_delta,
+                                            entropy_coef=entropy_coef)
         ga = torch.autograd.grad(pol - ent * entropy_coef, [pa[k] for k in NET_KEYS])
         gc = torch.autograd.grad(vloss * value_loss_coef, [pc[k] for k in NET_KEYS])
         ga, na = clip_grads(list(ga), max_norm)

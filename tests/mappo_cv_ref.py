@@ -61,7 +61,7 @@ def ppo_losses_cv(PA, PC, b, L, vn, clip=0.2, huber_delta=10.0):
 
 
 def ppo_train_cv(PA, PC, data, vn0, epochs, L, perms=None, dtype=torch.float32, lr=1e-4, eps=1e-5, max_norm=0.5,
-                 value_loss_coef=0.5, entropy_coef=0.01):
+                 value_loss_coef=0.5, entropy_coef=0.01, clip=0.2, huber_delta=10.0):
     """R_MAPPO.train (one minibatch per epoch) in ``dtype``; data in the reference layout [T(+1), E, N, ...] without
     share_obs; vn0 = (mean, mean_sq, debias). -> (record per epoch, PA2, PC2, vn)."""
     old = torch.get_default_dtype()
@@ -82,7 +82,7 @@ def ppo_train_cv(PA, PC, data, vn0, epochs, L, perms=None, dtype=torch.float32, 
             pa = {k: v.detach().clone().requires_grad_(True) for k, v in PA.items()}
             pc = {k: v.detach().clone().requires_grad_(True) for k, v in PC.items()}
             vn.update(b["returns"])
-            pol, ent, vloss, _ = ppo_losses_cv(pa, pc, b, L, vn)
+            pol, ent, vloss, _ = ppo_losses_cv(pa, pc, b, L, vn, clip=clip, huber_delta=huber_delta)
             ga = torch.autograd.grad(pol - ent * entropy_coef, [pa[k] for k in om.NET_KEYS])
             gc = torch.autograd.grad(vloss * value_loss_coef, [pc[k] for k in om.NET_KEYS])
             ga, na = om.clip_grads(list(ga), max_norm)

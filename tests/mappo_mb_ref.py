@@ -34,7 +34,8 @@ def minibatches(perm, M):
 
 
 def ppo_train_mb(PA, PC, data, vn0, epochs, L, perms, M, dtype=torch.float32, shuffle=False, cent=False,
-                 updates=None, lr=1e-4, eps=1e-5, max_norm=0.5, value_loss_coef=0.5, entropy_coef=0.01):
+                 updates=None, lr=1e-4, eps=1e-5, max_norm=0.5, value_loss_coef=0.5, entropy_coef=0.01,
+                 clip=0.2, huber_delta=10.0):
     """R_MAPPO.train with M minibatches per epoch in ``dtype``. data: the reference layout [T(+1), E, N, ...];
     perms [epochs, n_chunks] in the reference's chunk numbering; vn0 = (mean, mean_sq, debias). shuffle: the chunks
     of every minibatch in a fixed random order. cent: centralized critic on share_obs. updates: stop after that many.
@@ -63,9 +64,10 @@ def ppo_train_mb(PA, PC, data, vn0, epochs, L, perms, M, dtype=torch.float32, sh
                 vn.update(b["returns"])
                 if cent:
                     b["cent_obs"] = om.chunk_batch(dc, adv, L, order)["obs"]
-                    pol, ent, vloss, ratio = cv.ppo_losses_cv(pa, pc, b, L, vn)
+                    pol, ent, vloss, ratio = cv.ppo_losses_cv(pa, pc, b, L, vn, clip=clip, huber_delta=huber_delta)
                 else:
-                    pol, ent, vloss, ratio = om.ppo_losses(pa, pc, b, L, vn, entropy_coef=entropy_coef)
+                    pol, ent, vloss, ratio = om.ppo_losses(pa, pc, b, L, vn, clip=clip, huber_delta=huber_delta,
+                                                           entropy_coef=entropy_coef)
                 ga = torch.autograd.grad(pol - ent * entropy_coef, [pa[k] for k in om.NET_KEYS])
                 gc = torch.autograd.grad(vloss * value_loss_coef, [pc[k] for k in om.NET_KEYS])
                 ga, na = om.clip_grads(list(ga), max_norm)

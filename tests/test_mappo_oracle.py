@@ -60,16 +60,14 @@ def _train_data(fx):
     return {k[5:]: fx[k] for k in fx if k.startswith("data.")}
 
 
-@pytest.mark.parametrize("use_perm", [True, False])
-def test_ppo_train_golden(golden, use_perm):
-    fx = golden("mappo_train")
+def _check_ppo_train(fx, use_perm, **kw):
     PA, PC = _nets(fx, "before.")
     vn = om.ValueNorm(float(fx["vn0.running_mean"][0]), float(fx["vn0.running_mean_sq"][0]),
                       float(fx["vn0.debiasing_term"]))
     rec = []
     E = int(fx["epochs"])
     PA2, PC2, vn = om.ppo_train(PA, PC, _train_data(fx), vn, E, int(fx["L"]),
-                                perms=fx["perms"] if use_perm else None, record=rec)
+                                perms=fx["perms"] if use_perm else None, record=rec, **kw)
     # clipped gradients fed to each Adam step (reference names via om.ref_name)
     tol = dict(rtol=2e-4, atol=1e-7) if use_perm else dict(rtol=2e-3, atol=1e-6)
     for ep in range(E):
@@ -87,3 +85,26 @@ def test_ppo_train_golden(golden, use_perm):
                                    atol=2e-6)
     np.testing.assert_allclose(vn.m.numpy(), fx["vn1.running_mean"], rtol=1e-6)
     np.testing.assert_allclose(vn.msq.numpy(), fx["vn1.running_mean_sq"], rtol=1e-6)
+    return rec
+
+
+@pytest.mark.parametrize("use_perm", [True, False])
+def test_ppo_train_golden(golden, use_perm):
+    _check_ppo_train(golden("mappo_train"), use_perm)
+
+
+@pytest.mark.parametrize("use_perm", [True, False])
+def test_ppo_train_clip_golden(golden, use_perm):
+    """The reference's train() with the surrogate clip, the value clip and both Huber arms active
+    (tests/golden/make_golden_mappo_clip.py): pins torch.min / clamp / torch.max / huber of ppo_losses outside the
+    clip range, and the clip= / huber_delta= pass-through; the logged losses too (they are no longer those of a
+    ratio of 1)."""
+    fx = golden("mappo_clip_train")
+    clip, delta = float(fx["clip_param"]), float(fx["huber_delta"])
+    assert clip == 0.2 and 0.5 < delta < 2.0
+    rec = _check_ppo_train(fx, use_perm, clip=clip, huber_delta=delta)
+    for key, f in (("policy_loss", "pol"), ("value_loss", "vloss"), ("dist_entropy", "ent")):
+        np.testing.assert_allclose(np.mean([r[f] for r in rec]), float(fx["info." + key]), rtol=2e-5, atol=1e-7)
+    # the defaults (clip inactive on the value side, Huber quadratic everywhere) do NOT reproduce it
+    with pytest.raises(AssertionError):
+        _check_ppo_train(fx, use_perm, huber_delta=10.0)
