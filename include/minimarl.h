@@ -716,6 +716,41 @@ int mm_mappo_vn_update(float* vn, float* stats, double beta, mm_stream_t s);
 int mm_mappo_insert(const uint8_t* done, int32_t n_agents, int32_t hidden, int64_t n_envs, float* mask_next,
                     float* active_next, float* h_actor, float* h_critic, uint64_t* counter, mm_stream_t s);
 
+/* ---- Feed-forward MAPPO (the reference's algorithm_name "mappo": use_recurrent_policy and
+ * use_naive_recurrent_policy False, mappo/main.py:62-65; R_Actor / R_Critic without their RNNLayer,
+ * r_actor_critic.py:46,84,123,168,204). The nets are the LN-MLP trunk followed directly by the head,
+ * out = Wo LN2(relu(W2 LN1(relu(W1 LN0(obs) + b1)) + b2)) + bo: no GRU and no post-GRU LayerNorm; hidden states and
+ * masks are never read. mm_mappo_dims, the argument structs and the flat 18-tensor layout of mm_mappo_param_offsets
+ * are the recurrent path's: the six recurrent tensors (Wih Whh bih bhh lnr_w lnr_b) are not read and receive exactly
+ * zero gradient (kept at zero, mm_clip_adam leaves them there and the gradient norm is unaffected). Same supported
+ * shapes: H 32, A 5, obs_dim 47 | 94, a centralized critic of 2 or 8 agents at obs_dim 47; anything else is an error.
+ *
+ * mm_mappo_ff_fwd: get_actions / get_values (rmappo_policy.py:57-99) of mm_mappo_fwd's modes MM_MAPPO_ROLLOUT (sample
+ * with u or the counter RNG keyed (seed, counter, row), evaluate act_in, or deterministic = first argmax; actor
+ * log-prob and critic value per row) and MM_MAPPO_VALUES (critic only). net[].h_in, net[].h_out and mask are ignored
+ * and may be NULL. MM_MAPPO_TRAIN is refused. */
+int mm_mappo_ff_fwd(const mm_mappo_dims* d, const mm_mappo_fwd_args* a, mm_stream_t s);
+/* One PPO update's gradients of both nets in one row-parallel pass (ramppo_network.py:56-209 over a batch of
+ * feed_forward_generator, shared_buffer.py:159-219): per row the forward recomputed from obs, the loss seed on
+ * stats[MM_MST_ADV_MEAN / ADV_STD / ACTIVE_SUM / VN_MEAN / VN_STD], the head's and the LN-MLP's backward, weight
+ * gradients reduced in-kernel and summed in a fixed order (two equal calls are bit-identical). rows NULL: all T * en
+ * buffer rows in buffer order. Else a device int32[n_rows] list of buffer rows t * en + e (one minibatch; the
+ * reference numbers rows the same way, reshape(-1) of [T, E, N]); entries must be distinct and in [0, T * en), they
+ * are not checked on the device; needs 1 <= n_rows <= T * en < 2^31; the list 0 .. T * en - 1 reproduces rows = NULL
+ * bit for bit. A centralized critic row reads its env's adjacent obs rows from the buffer whether or not they are
+ * listed. Seeds divide by stats[MM_MST_ACTIVE_SUM] (a minibatch's: mm_mappo_mb_stats with L = 1, whose chunk numbers
+ * are then buffer rows). Uses a's P, obs, cent_obs, active, act, adv, old_logp, old_value, returns, stats, loss_acc,
+ * coefficients, en, T (mask, L, save / gsoa / rs ignored). A row list with cent_agents 8 is refused (an error, no
+ * launch): only rows = NULL runs the 376-wide critic. Writes the full flat gradient vectors. scratch:
+ * mm_mappo_ff_grad_scratch_count(d) floats (-1: unsupported dims), 16-byte aligned. */
+int64_t mm_mappo_ff_grad_scratch_count(const mm_mappo_dims* d);
+int mm_mappo_ff_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const int32_t* rows, int64_t n_rows,
+                     float* grad_actor, float* grad_critic, float* scratch, mm_stream_t s);
+/* mm_mappo_insert without hidden states: masks / active of slot t+1 from done [E] u8; increments the device RNG step
+ * counter (u64, may be NULL). */
+int mm_mappo_ff_insert(const uint8_t* done, int32_t n_agents, int64_t n_envs, float* mask_next, float* active_next,
+                       uint64_t* counter, mm_stream_t s);
+
 /* ------------------------------------------------------------------ offpolicy episode QMix / VDN
  * Replaces QMix.train_policy_on_batch (offpolicy/algorithms/qmix/qmix.py:80-210) with the shared
  * QMixPolicy (algorithm/QMixPolicy.py:51-195; AgentQFunction = LN(D) -> [Linear, ReLU, LN] x 2 ->

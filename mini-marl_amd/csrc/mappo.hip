@@ -695,6 +695,17 @@ __global__ __launch_bounds__(256) void mappo_insert_kernel(const uint8_t* __rest
   }
 }
 
+// The same insert for feed-forward nets (no hidden states to zero): one thread per (env, agent) row.
+__global__ __launch_bounds__(256) void mappo_ff_insert_kernel(const uint8_t* __restrict__ done, int N, int64_t E,
+                                                              float* __restrict__ mask_next,
+                                                              float* __restrict__ active_next, uint64_t* counter) {
+  const int64_t row = blockIdx.x * 256ll + threadIdx.x;
+  if (row == 0 && counter) *counter += 1;  // device RNG step counter of the next rollout step
+  if (row >= E * N) return;
+  mask_next[row] = done[row / N] != 0 ? 0.0f : 1.0f;
+  active_next[row] = 1.0f;
+}
+
 // ------------------------------------------------------------------ host dispatch
 int mappo_roll_fwd(const mm_mappo_dims* d, const mm_mappo_fwd_args* a, hipStream_t s);   // mappo_grad.hip
 
@@ -985,6 +996,17 @@ int mm_mappo_insert(const uint8_t* done, int32_t n_agents, int32_t hidden, int64
   const int64_t n = n_envs * n_agents * hidden;
   hipLaunchKernelGGL(mm::mappo_insert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, done,
                      n_agents, hidden, n_envs, mask_next, active_next, h_actor, h_critic, counter);
+  MM_HIP_CHECK(hipGetLastError());
+  return MM_OK;
+}
+
+int mm_mappo_ff_insert(const uint8_t* done, int32_t n_agents, int64_t n_envs, float* mask_next, float* active_next,
+                       uint64_t* counter, mm_stream_t s) {
+  MM_REQUIRE(done && mask_next && active_next, "mappo_ff_insert: null pointer");
+  MM_REQUIRE(n_agents > 0 && n_envs > 0, "mappo_ff_insert: need n_agents > 0 and n_envs > 0");
+  const int64_t n = n_envs * n_agents;
+  hipLaunchKernelGGL(mm::mappo_ff_insert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, done,
+                     n_agents, n_envs, mask_next, active_next, counter);
   MM_HIP_CHECK(hipGetLastError());
   return MM_OK;
 }

@@ -31,6 +31,9 @@
 // and drops the parking of the MLP activations the single-pass kernel needed.
 // Minibatch variant (mm_mappo_grad_mb, the *_mb kernels): the same two bodies with IDX = true run over a list of
 // chunks (one PPO minibatch of recurrent_generator's sampler) instead of all of them.
+// Feed-forward nets (algorithm_name "mappo": no GRU, no LN_r; mm_mappo_ff_fwd / mm_mappo_ff_grad, at the end of the
+// namespace): a rollout forward without the recurrent part and one row-parallel gradient pass, pass M's body with
+// the head and the loss seed in registers, over all rows or a row list.
 #include <algorithm>
 
 #include "common.h"
@@ -1677,6 +1680,593 @@ struct GradShape {
   }
 };
 
+// ---------------------------------------------------------------- feed-forward nets (algorithm_name "mappo")
+// use_recurrent_policy = use_naive_recurrent_policy = False (mappo/main.py:62-65): R_Actor / R_Critic without their
+// RNNLayer (r_actor_critic.py:46,84,123,168,204): out = Wo x2 + bo on the LN-MLP's x2 = LN2(a2), no GRU and no
+// post-GRU LayerNorm (rnn.py:79 belongs to the RNNLayer); hiddens and masks are never read. The flat parameter
+// layout stays MGeo's 18 tensors; the six recurrent ones are not read and get exactly zero gradient.
+//
+// Rollout / values forward (mappo_ff_roll_kernel): roll_body without the h_in load, the Gru and LN_r; the same
+// exact-f32 v_mfma_f32_32x32x2_f32 trunk (Mlp), 4 waves per block, blockIdx.y = net. Its LDS image holds the MLP
+// rows at Geo's offsets (Mlp reads them there), then the MLP's vectors (LnOff) and the head.
+template <int D, int O>
+struct GeoF {
+  using G = Geo<D, O>;
+  static constexpr int W1 = G::W1, W2 = G::W2, ln0w = W2 + 32 * G::PW, Wo = ln0w + LnOff<D>::ln2b + 32,
+                       bo = Wo + 8 * 32, total = bo + 8;
+  static_assert(G::bih - G::ln0w == LnOff<D>::ln2b + 32 && G::scr - G::Wo == 8 * 32 + 8, "Geo's vector blocks");
+};
+static_assert(GeoF<47, 5>::total * 4 <= 160 * 1024 && GeoF<94, 5>::total * 4 <= 160 * 1024 &&
+                  GeoF<94, 1>::total * 4 <= 160 * 1024 && GeoF<376, 1>::total * 4 <= 160 * 1024,
+              "LDS budget of the feed-forward rollout image");
+
+template <int D, int O>
+__device__ void stage_ff(float* sm, const float* __restrict__ P) {
+  using G = Geo<D, O>;
+  using GF = GeoF<D, O>;
+  for (int e = threadIdx.x; e < GF::total; e += blockDim.x) {
+    const int src = e < GF::ln0w ? e : (e < GF::Wo ? G::ln0w + (e - GF::ln0w) : G::Wo + (e - GF::Wo));
+    sm[e] = stage_value<D, O>(P, src);
+  }
+  __syncthreads();
+}
+
+template <int D, int A, int O, int NA = 1>
+__device__ void roll_ff_body(const mm_mappo_fwd_args& a, int net, float* sm) {
+  using GF = GeoF<D, O>;
+  stage_ff<D, O>(sm, a.net[net].P);
+  const mm_mappo_net_io& io = a.net[net];
+  const int lane = (int)(threadIdx.x & 63), ci = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t R = a.rows, ntile = (R + 31) / 32;
+  const uint64_t ctr = a.counter_ptr ? *a.counter_ptr : a.counter;
+  for (int64_t tile = (int64_t)blockIdx.x * 4 + w; tile < ntile; tile += (int64_t)gridDim.x * 4) {
+    const int64_t r0 = tile * 32 + ci;
+    const bool valid = r0 < R;
+    const int64_t row = valid ? r0 : R - 1;
+    const float* smo = sm + opaque0();
+    float x2[16];
+    {
+      Mlp<D, O, (NA > 1)> mp;
+      mp.run(smo + GF::W1, smo + GF::W2, smo + GF::ln0w, in_row<D, NA>(a.obs, a.cent_obs, row));
+      mp.x2(smo + GF::ln0w, x2);
+    }
+    // head on x2: Wo x2 + bo
+    float l[O];
+#pragma unroll
+    for (int o = 0; o < O; ++o) {
+      float sacc = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) sacc = fmaf(smo[GF::Wo + o * 32 + kperm(q, h)], x2[q], sacc);
+      l[o] = smo[GF::bo + o] + xsum(sacc);
+    }
+    if (!valid || h != 0) continue;
+    if constexpr (O == 1) {
+      if (io.out) io.out[row] = l[0];
+    } else {
+      // log-softmax, then the given action, the mode or the inverse-CDF sample (roll_body's arithmetic)
+      float mx = l[0];
+#pragma unroll
+      for (int q = 1; q < O; ++q) mx = fmaxf(mx, l[q]);
+      float se = 0.0f;
+#pragma unroll
+      for (int q = 0; q < O; ++q) se += expf(l[q] - mx);
+      const float lse = mx + logf(se);
+#pragma unroll
+      for (int q = 0; q < O; ++q) l[q] -= lse;
+      int act;
+      if (a.act_in) {
+        act = a.act_in[row];
+      } else if (a.deterministic) {
+        act = 0;   // Categorical.mode() = first argmax (distributions.py:61-62)
+#pragma unroll
+        for (int q = 1; q < O; ++q)
+          if (l[q] > l[act]) act = q;
+        if (a.act_out) a.act_out[row] = act;
+      } else {
+        const float u = a.u ? a.u[row] : rng_uniform(rng_draw(a.seed, ctr, (uint64_t)row, 0x9E37ull));
+        act = O - 1;   // inverse CDF: first k with u < cumsum(p)[k], the last action if rounding leaves none
+        bool found = false;
+        float cs = 0.0f;
+#pragma unroll
+        for (int q = 0; q < O; ++q) {
+          cs += expf(l[q]);
+          if (!found && u < cs) {
+            act = q;
+            found = true;
+          }
+        }
+        if (a.act_out) a.act_out[row] = act;
+      }
+      float lp = l[0];
+#pragma unroll
+      for (int q = 1; q < O; ++q)
+        if (q == act) lp = l[q];
+      if (io.out) io.out[row] = lp;
+    }
+  }
+}
+
+template <int D, int A, int NA>
+constexpr int roll_ff_lds() {
+  return std::max(GeoF<D, A>::total, GeoF<D * NA, 1>::total) * 4;
+}
+template <int D, int A, int NA>
+__global__ __launch_bounds__(256, (2 * roll_ff_lds<D, A, NA>() <= 160 * 1024 ? 2 : 1)) void mappo_ff_roll_kernel(
+    mm_mappo_fwd_args a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int net = (int)blockIdx.y + (a.mode == MM_MAPPO_VALUES ? 1 : 0);
+  if (net == 0)
+    roll_ff_body<D, A, A>(a, 0, sm);
+  else
+    roll_ff_body<D * NA, A, 1, NA>(a, 1, sm);
+}
+
+template <int D, int A, int NA>
+static int roll_ff_fwd(const mm_mappo_fwd_args* a, hipStream_t s) {
+  constexpr size_t lds = (size_t)roll_ff_lds<D, A, NA>();
+  static_assert(lds <= 160 * 1024, "LDS budget");
+  static const int attr_rc = [&]() -> int {
+    MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_ff_roll_kernel<D, A, NA>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MM_OK;
+  }();
+  if (attr_rc != MM_OK) return attr_rc;
+  if (a->rows <= 0) return MM_OK;
+  const int64_t ntile = (a->rows + 31) / 32;
+  const int nets = a->mode == MM_MAPPO_VALUES ? 1 : 2;
+  const unsigned nb = (unsigned)std::min<int64_t>((ntile + 3) / 4, 1024);   // beyond 131072 rows: a 2nd tile per wave
+  hipLaunchKernelGGL((mappo_ff_roll_kernel<D, A, NA>), dim3(nb, nets), dim3(256), lds, s, *a);
+  MM_HIP_CHECK(hipGetLastError());
+  return MM_OK;
+}
+
+// Gradient pass (mappo_ff_grad_kernel, one launch per update, row-parallel): pass M's body with the head in
+// registers in place of the d x2 load. Per tile of 32 rows: the LN-MLP forward on pass M's split image (MlpH, fp16x3
+// products), the logits / value from the recomputed x2 (fp32 FMAs: the head is at most 5 wide), the row's PPO / Huber
+// loss seed (gru_body's arithmetic on stats[ADV_MEAN / ADV_STD / ACTIVE_SUM / VN_MEAN / VN_STD]), dWo += dout x2^T
+// and dbo, d x2 = Wo^T dout, and from there pass M unchanged. No d x2 scratch, no parked activations. Image: GeoM's
+// (stage_h<.., true>), then the f32 head, then the wave transpose tiles.
+// IDX: tile t's lane ci handles buffer row rows[32 t + ci] of a list of n_rows (one PPO minibatch of
+// feed_forward_generator, shared_buffer.py:159-219) instead of row 32 t + ci of all T EN; the list 0 .. T EN - 1
+// gives the same tiles and summation order. A centralized critic row reads its env's NA adjacent obs rows from the
+// buffer whether or not they are listed. Tail lanes (clamped to the last row) carry a zero seed: zero in dWo, dbo,
+// d x2, the loss sums and every column sum.
+template <int D, int O>
+struct GeoFM {
+  using GM = GeoM<D, O>;
+  static constexpr int DT = GM::DT;
+  static constexpr int Wo = GM::scr, bo = Wo + 8 * 32, scr = bo + 8;
+  // waves per block: 4 (1 per SIMD, 512 VGPRs each) where the tiles fit the 160 KB of LDS, else 3 (D 376). Pass M's 8
+  // (2 per SIMD, 256 VGPRs) is not taken: the head's live state on top of pass M's (seeds, d x2, the dWo / dbo and
+  // loss sums) does not fit 256 registers (about 80 VGPRs spilled at D 47)
+  static constexpr int MW = (scr + 4 * MT * TILE) * 4 <= 160 * 1024 ? 4 : 3;
+  static constexpr int total_for(int mw) { return scr + mw * MT * TILE; }
+  static_assert(scr % 4 == 0, "16-byte aligned transpose tiles");
+  static_assert(total_for(MW) * 4 <= 160 * 1024, "LDS budget of the feed-forward gradient image");
+  static_assert(MGeo<D, H, O>::total <= total_for(MW), "the block reduction reuses the image");
+};
+static_assert(GeoFM<47, 5>::MW == 4 && GeoFM<94, 5>::MW == 4 && GeoFM<94, 1>::MW == 4 && GeoFM<376, 1>::MW == 3,
+              "waves per block of the feed-forward gradient pass");
+
+struct FfGradArgs {
+  mm_mappo_bwd_args a;
+  float* partial;        // [2][NB][pstride]
+  int64_t pstride;
+  const int32_t* rows;   // IDX: [n_rows] buffer rows t * EN + en
+  int64_t n_rows;
+};
+
+template <int D, int A, int O, int MWV, int NA = 1, bool IDX = false>
+__device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
+  using GM = GeoM<D, O>;
+  using GF = GeoFM<D, O>;
+  constexpr bool WIDE = NA > 1;
+  using F = MGeo<D, H, O>;
+  using LO = LnOff<D>;
+  constexpr int DT = GM::DT;
+  const mm_mappo_bwd_args& a = k.a;
+  stage_h<D, O, true>(sm, a.P[net]);
+  for (int e = threadIdx.x; e < 8 * 32 + 8; e += blockDim.x) sm[GF::Wo + e] = stage_value<D, O>(a.P[net], Geo<D, O>::Wo + e);
+  __syncthreads();
+  const int lane = (int)(threadIdx.x & 63), ci = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  float* S0 = sm + GF::scr + w * MT * TILE;
+  float* S1 = S0 + TILE;
+  float* S2 = S1 + TILE;
+  const int64_t R = IDX ? k.n_rows : (int64_t)a.T * a.en, ntile = (R + 31) / 32;
+  const int wg = blockIdx.x * MWV + w, nwg = gridDim.x * MWV;
+  const float inv_m = 1.0f / a.stats[MM_MST_ACTIVE_SUM];
+
+  f32x16 aW2, aW1[DT];
+  zero16(aW2);
+#pragma unroll
+  for (int t = 0; t < DT; ++t) zero16(aW1[t]);
+  float sb2 = 0.f, sb1 = 0.f, sl2w = 0.f, sl2b = 0.f, sl1w = 0.f, sl1b = 0.f, sl0w[DT], sl0b[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t) sl0w[t] = sl0b[t] = 0.f;
+  // head: lane (i, h) sums dWo[o][i] over the rows 2 s + h of its tiles; lane c (h = 0) sums dbo over its rows
+  float aWo[O], sbo[O];
+#pragma unroll
+  for (int o = 0; o < O; ++o) aWo[o] = sbo[o] = 0.f;
+  float lsum0 = 0.f, lsum1 = 0.f, lsum2 = 0.f;
+
+  for (int64_t tile = wg; tile < ntile; tile += nwg) {
+    const int64_t r = tile * 32 + ci;
+    const bool valid = r < R;
+    int64_t row = valid ? r : R - 1;
+    if constexpr (IDX) row = k.rows[row];
+    const float* smb = sm + opaque0();
+    const float* lv = smb + GM::ln0w;
+    const float sw = smb[GM::wsc], s_f0 = smb[GM::wsc + 1], s_f1 = smb[GM::wsc + 2];
+    const float* __restrict__ orow = in_row<D, NA>(a.obs, a.cent_obs, row);
+    MlpH<D, GM, WIDE> mp;
+    mp.run(smb, orow);
+    // ---- head: out = Wo x2 + bo on the recomputed x2 = LN2(a2)
+    float dxv[16];
+    {
+      // (the head's LDS reads start here: not hoisted into the forward above, where the registers are full)
+      __builtin_amdgcn_sched_barrier(0);
+      const float* smh = sm + opaque0();
+      float x2[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+        x2[q] = (mp.a2[q] - mp.mu2) * mp.rs2 * smh[GM::ln0w + LO::ln2w + kperm(q, h)] +
+                smh[GM::ln0w + LO::ln2b + kperm(q, h)];
+      float out[O];
+#pragma unroll
+      for (int o = 0; o < O; ++o) {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s = fmaf(smh[GF::Wo + o * 32 + kperm(q, h)], x2[q], s);
+        out[o] = smh[GF::bo + o] + xsum(s);
+      }
+      // ---- loss seed d(out) (gru_body's; ramppo_network.py:56-209)
+      const float m = valid ? a.active[row] : 0.f;
+      float dout[O];
+      if constexpr (O == A) {
+        float mx = out[0];
+#pragma unroll
+        for (int q = 1; q < A; ++q) mx = fmaxf(mx, out[q]);
+        float se = 0.f;
+#pragma unroll
+        for (int q = 0; q < A; ++q) se += expf(out[q] - mx);
+        const float lse = mx + logf(se);
+        float lp[A], ent = 0.f;
+#pragma unroll
+        for (int q = 0; q < A; ++q) {
+          lp[q] = out[q] - lse;
+          ent -= expf(lp[q]) * lp[q];
+        }
+        const int act = a.act[row];
+        float lpa = lp[0];
+#pragma unroll
+        for (int q = 1; q < A; ++q)
+          if (q == act) lpa = lp[q];
+        const float adv = (a.adv[row] - a.stats[MM_MST_ADV_MEAN]) / (a.stats[MM_MST_ADV_STD] + 1e-5f);
+        const float ratio = expf(lpa - a.old_logp[row]);
+        const float s1 = ratio * adv;
+        const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
+        const float s2 = rc * adv;
+        const float inr = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
+        // torch.min backward: the smaller side gets the gradient, ties split it in half
+        const float g = s1 < s2 ? 1.0f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
+        const float dlpa = -m * inv_m * adv * ratio * g;
+        const float dent = -a.entropy_coef * m * inv_m;
+        const bool cnt = h == 0 && valid;   // (selects, not a divergent region)
+        lsum0 += cnt ? -fminf(s1, s2) * m : 0.f;
+        lsum1 += cnt ? ent * m : 0.f;
+        lsum2 += cnt ? ratio : 0.f;
+#pragma unroll
+        for (int q = 0; q < A; ++q) {
+          const float p = expf(lp[q]);
+          dout[q] = dlpa * ((q == act ? 1.0f : 0.0f) - p) + dent * (-p * (lp[q] + ent));
+        }
+      } else {
+        const float v = out[0];
+        const float old = a.old_value[row];
+        const float tgt = (a.returns[row] - a.stats[MM_MST_VN_MEAN]) / a.stats[MM_MST_VN_STD];
+        const float dv = v - old;
+        const float vc = old + fminf(fmaxf(dv, -a.clip), a.clip);
+        const float eo = tgt - v, ec = tgt - vc;
+        const float hd = a.huber_delta;
+        const float lo = fabsf(eo) <= hd ? eo * eo * 0.5f : hd * (fabsf(eo) - hd * 0.5f);
+        const float lc = fabsf(ec) <= hd ? ec * ec * 0.5f : hd * (fabsf(ec) - hd * 0.5f);
+        const float go = -(fabsf(eo) <= hd ? eo : (eo > 0.f ? hd : -hd));
+        const float gc =
+            -(fabsf(ec) <= hd ? ec : (ec > 0.f ? hd : -hd)) * ((dv >= -a.clip && dv <= a.clip) ? 1.0f : 0.0f);
+        const float d = lo > lc ? go : (lc > lo ? gc : 0.5f * (go + gc));
+        dout[0] = a.value_coef * m * inv_m * d;
+        lsum0 += (h == 0 && valid) ? fmaxf(lo, lc) * m : 0.f;
+      }
+      if (!valid) {   // a tail lane: an exact zero whatever the clamped row holds
+#pragma unroll
+        for (int o = 0; o < O; ++o) dout[o] = 0.f;
+      }
+      // ---- d x2 = Wo^T dout; dWo += dout x2^T (x2 transposed through S1, the tile's seeds as [row][8] in S2), dbo
+      const float* smw = sm + opaque0();   // (Wo is read again, not kept in registers across the seed)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        float s = 0.f;
+#pragma unroll
+        for (int o = 0; o < O; ++o) s = fmaf(smw[GF::Wo + o * 32 + kperm(q, h)], dout[o], s);
+        dxv[q] = s;
+      }
+      tput(S1, x2);
+      // (no divergent region here: a row's two lanes hold the same seeds and both store them)
+#pragma unroll
+      for (int o = 0; o < O; ++o) {
+        S2[ci * 8 + o] = dout[o];
+        sbo[o] += h == 0 ? dout[o] : 0.f;
+      }
+      wave_fence();
+      // (tget's addressing; 4 rows in flight: fully unrolled, the 16 x (O + 1) LDS reads are all issued up front and spill)
+      const float* xp = S1 + h * TP + ci;
+      const float* dr = S2 + h * 8;
+#pragma unroll 4
+      for (int s = 0; s < 16; ++s) {
+        const float xv = xp[2 * s * TP];
+#pragma unroll
+        for (int o = 0; o < O; ++o) aWo[o] = fmaf(dr[16 * s + o], xv, aWo[o]);
+      }
+      wave_fence();
+    }
+    // ---- from here pass M (mlp_body): LN2 backward (x2 = LN2(a2), a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
+    float da[16], xh[16], tt[16], f1[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) xh[q] = (mp.a2[q] - mp.mu2) * mp.rs2;
+    ln32_bwd(dxv, xh, mp.rs2, lv + LO::ln2w, da);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      tt[q] = dxv[q] * xh[q];
+      da[q] = mp.a2[q] > 0.f ? da[q] : 0.f;
+      xh[q] = (mp.a1[q] - mp.mu1) * mp.rs1;
+      f1[q] = xh[q] * lv[LO::ln1w + kperm(q, h)] + lv[LO::ln1b + kperm(q, h)];
+    }
+    tput(S0, da);
+    tput(S1, f1);
+    tput(S2, tt);
+    const float s_a2 = scale_for(wave_max(absmax16(da)));
+    // ---- LN1 backward: dx1 = W2^T da2 (one scale per column), then da1
+    float dx1[16], da1[16];
+    {
+      const float c_a = scale_for(col_max(absmax16(da)));
+      S16 sa;
+      split16s(da, c_a, sa);
+      f32x16 acc;
+      zero16(acc);
+      mmh(smb + GM::W2T, sa, acc);
+      const float u = 1.0f / (sw * c_a);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dx1[q] = acc[q] * u;
+      ln32_bwd(dx1, xh, mp.rs1, lv + LO::ln1w, da1);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        tt[q] = dx1[q] * xh[q];
+        da1[q] = mp.a1[q] > 0.f ? da1[q] : 0.f;
+      }
+    }
+    wave_fence();
+    // dW2 += da2 f1^T, db2
+    float At[16];
+    {
+      float Bt[16];
+      tget(S0, At);
+      tget(S1, Bt);
+      sl2w += tsum(S2);
+      wave_fence();
+      tput(S0, da1);
+      tput(S1, dxv);
+      tput(S2, tt);
+      S16 sa, sb;
+      split16s(At, s_a2, sa);
+      split16s(Bt, s_f1, sb);
+      f32x16 tmp;
+      zero16(tmp);
+      accg(tmp, sa, sb);
+      acc_unscale(aW2, tmp, 1.0f / (s_a2 * s_f1));
+#pragma unroll
+      for (int s = 0; s < 16; ++s) sb2 += At[s];
+    }
+    const float s_a1 = scale_for(wave_max(absmax16(da1)));
+    wave_fence();
+    sl2b += tsum(S1);
+    sl1w += tsum(S2);
+    tget(S0, At);   // da1 transposed
+    wave_fence();
+    tput(S1, dx1);
+    wave_fence();
+    sl1b += tsum(S1);
+    wave_fence();
+    // ---- L1 / LN0: dW1 += da1 f0^T, db1, df0 = W1^T da1 -> LN0 parameter gradients
+    {
+      S16 sa;
+      split16s(At, s_a1, sa);
+#pragma unroll
+      for (int s = 0; s < 16; ++s) sb1 += At[s];
+      const float c_b = scale_for(col_max(absmax16(da1)));
+      S16 sd;
+      split16s(da1, c_b, sd);
+      const float u_b = 1.0f / (sw * c_b), u_w = 1.0f / (s_a1 * s_f0);
+      float x[WIDE ? 1 : DT][16];
+      if constexpr (!WIDE) load_obs<D, DT>(orow, x);
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        float x0[16], f0[16], dfv[16];
+        if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);   // (streamed again: the wide row is not kept)
+        const float (&xt)[16] = x[WIDE ? 0 : t];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int f = 32 * t + kperm(q, h);
+          x0[q] = (xt[q] - mp.mu0) * mp.rs0;
+          f0[q] = x0[q] * lv[LO::ln0w + f] + lv[LO::ln0b + f];
+        }
+        tput(S0, f0);
+        f32x16 acc;
+        zero16(acc);
+        mmh(smb + GM::W1T + t * HBLK, sd, acc);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          dfv[q] = acc[q] * u_b;
+          tt[q] = dfv[q] * x0[q];
+        }
+        tput(S1, tt);
+        tput(S2, dfv);
+        wave_fence();
+        float Bt[16];
+        tget(S0, Bt);
+        sl0w[t] += tsum(S1);
+        sl0b[t] += tsum(S2);
+        S16 sb;
+        split16s(Bt, s_f0, sb);
+        f32x16 tmp;
+        zero16(tmp);
+        accg(tmp, sa, sb);
+        acc_unscale(aW1[t], tmp, u_w);
+        wave_fence();
+      }
+    }
+  }
+
+  // ---- loss sums (logging only, train_info): one atomic per wave
+  if (a.loss_acc) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lsum0 += __shfl_xor(lsum0, o);
+      lsum1 += __shfl_xor(lsum1, o);
+      lsum2 += __shfl_xor(lsum2, o);
+    }
+    if (lane == 0) {
+      if constexpr (O == A) {
+        atomicAdd(&a.loss_acc[MM_MLOSS_POLICY], lsum0 * inv_m);
+        atomicAdd(&a.loss_acc[MM_MLOSS_ENTROPY], lsum1 * inv_m);
+        atomicAdd(&a.loss_acc[MM_MLOSS_RATIO], lsum2);
+      } else {
+        atomicAdd(&a.loss_acc[MM_MLOSS_VALUE], lsum0 * inv_m);
+      }
+    }
+  }
+
+  // ---- block reduction (fixed order) into the flat gradient layout (the recurrent tensors stay zero), one partial
+  __syncthreads();
+  float* red = sm;
+  for (int e = threadIdx.x; e < F::total; e += blockDim.x) red[e] = 0.f;
+  sb2 = xsum(sb2);
+  sb1 = xsum(sb1);
+  sl2w = xsum(sl2w);
+  sl2b = xsum(sl2b);
+  sl1w = xsum(sl1w);
+  sl1b = xsum(sl1b);
+#pragma unroll
+  for (int t = 0; t < DT; ++t) {
+    sl0w[t] = xsum(sl0w[t]);
+    sl0b[t] = xsum(sl0b[t]);
+  }
+#pragma unroll
+  for (int o = 0; o < O; ++o) {
+    aWo[o] = xsum(aWo[o]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sbo[o] += __shfl_xor(sbo[o], d);
+  }
+  __syncthreads();
+  for (int ww = 0; ww < MWV; ++ww) {
+    if (w == ww) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int mm = kperm(q, h);
+        red[F::W2 + mm * H + ci] += aW2[q];
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+          if (32 * t + ci < D) red[F::W1 + mm * F::Dp + 32 * t + ci] += aW1[t][q];
+      }
+      if (h == 0) {
+        red[F::b2 + ci] += sb2;
+        red[F::b1 + ci] += sb1;
+        red[F::ln2_w + ci] += sl2w;
+        red[F::ln2_b + ci] += sl2b;
+        red[F::ln1_w + ci] += sl1w;
+        red[F::ln1_b + ci] += sl1b;
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+          if (32 * t + ci < D) {
+            red[F::ln0_w + 32 * t + ci] += sl0w[t];
+            red[F::ln0_b + 32 * t + ci] += sl0b[t];
+          }
+#pragma unroll
+        for (int o = 0; o < O; ++o) {
+          red[F::Wo + o * H + ci] += aWo[o];
+          if (ci == o) red[F::bo + o] += sbo[o];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  float* outp = k.partial + ((int64_t)net * NB + blockIdx.x) * k.pstride;
+  for (int e = threadIdx.x; e < F::total; e += blockDim.x) outp[e] = red[e];
+}
+
+// waves per block: one launch runs both nets, so the fewer of the two images' (mlp_waves' rule on GeoFM)
+template <int D, int A, int NA>
+constexpr int ffg_waves() {
+  return std::min(GeoFM<D, A>::MW, GeoFM<D * NA, 1>::MW);
+}
+
+template <int D, int A, int NA, bool IDX>
+__global__ __launch_bounds__((64 * ffg_waves<D, A, NA>()), 1) void mappo_ff_grad_kernel(FfGradArgs k) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int MW = ffg_waves<D, A, NA>();
+  if (blockIdx.y == 0)
+    ffg_body<D, A, A, MW, 1, IDX>(k, 0, sm);
+  else
+    ffg_body<D * NA, A, 1, MW, NA, IDX>(k, 1, sm);
+}
+
+template <int D, int A, int NA>
+struct FfGradShape {
+  static constexpr int DC = D * NA, MW = ffg_waves<D, A, NA>();
+  static constexpr int n0 = MGeo<D, H, A>::total, n1 = MGeo<DC, H, 1>::total;
+  static int64_t pstride() { return ((int64_t)std::max(n0, n1) + 3) & ~3ll; }
+  static int64_t scratch() { return 2ll * NB * pstride(); }
+  template <bool IDX>
+  static int launch(const FfGradArgs& k, float* ga, float* gc, hipStream_t s) {
+    constexpr size_t lds = (size_t)std::max(GeoFM<D, A>::total_for(MW), GeoFM<DC, 1>::total_for(MW)) * 4;
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert(std::max(n0, n1) * 4 <= (int)lds, "the block reduction reuses the image");
+    static const int attr_rc = [&]() -> int {
+      MM_HIP_CHECK(hipFuncSetAttribute((const void*)mappo_ff_grad_kernel<D, A, NA, IDX>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      return MM_OK;
+    }();
+    if (attr_rc != MM_OK) return attr_rc;
+    hipLaunchKernelGGL((mappo_ff_grad_kernel<D, A, NA, IDX>), dim3(NB, 2), dim3(64 * MW), lds, s, k);
+    MM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mappo_grad_sum_kernel, dim3((std::max(n0, n1) + 255) / 256, 2), dim3(256), 0, s, k.partial, NB,
+                       k.pstride, n0, n1, ga, gc);
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
+  }
+  static int run(const mm_mappo_bwd_args* a, const int32_t* rows, int64_t n_rows, float* ga, float* gc,
+                 float* scratch, hipStream_t s) {
+    FfGradArgs k = {};
+    k.a = *a;
+    k.partial = scratch;
+    k.pstride = pstride();
+    k.rows = rows;
+    k.n_rows = n_rows;
+    if (!rows) return launch<false>(k, ga, gc, s);
+    // The row-list pass of the 376-wide critic (3 waves per block, 33 VGPRs in scratch) is not instantiated: on the
+    // MI355X it gave gradients that differed from call to call on equal inputs (about 1e-6 relative, beyond the fp32
+    // bars at small batches) while the all-rows pass is repeatable; the cause is not established.
+    if constexpr (NA >= 8) {
+      set_error("mappo_ff_grad: a row list is not supported with cent_agents=%d (critic input width %d); pass "
+                "rows = NULL (one update over all rows)", NA, DC);
+      return MM_EINVAL;
+    } else {
+      return launch<true>(k, ga, gc, s);
+    }
+  }
+};
+
 }  // namespace mgr
 
 // (obs_dim, critic agents) of the instantiated shapes; the critic agents are 1 for a decentralized critic
@@ -1748,6 +2338,49 @@ int mm_mappo_grad_mb(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const i
 #define MM_CALL(D, N)                                                                                             \
   mm::mgr::GradShape<D, 5, N>::run_mb(a, chunks, n_chunks, h_actor, h_critic, grad_actor, grad_critic, scratch, \
                                       (hipStream_t)s)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  return mm::mappo_dims_error(d);
+}
+
+// ---- feed-forward nets (algorithm_name "mappo")
+int mm_mappo_ff_fwd(const mm_mappo_dims* d, const mm_mappo_fwd_args* a, mm_stream_t s) {
+  MM_REQUIRE(d && a, "mappo_ff_fwd: null argument");
+  MM_REQUIRE(a->mode == MM_MAPPO_ROLLOUT || a->mode == MM_MAPPO_VALUES, "mappo_ff_fwd: mode must be ROLLOUT or VALUES");
+  MM_REQUIRE(a->obs && a->net[1].P, "mappo_ff_fwd: obs / critic params required");
+  MM_REQUIRE(a->mode == MM_MAPPO_VALUES || a->net[0].P, "mappo_ff_fwd: actor params required");
+  if (!mm::mappo_dims_supported(d)) return mm::mappo_dims_error(d);
+  const int rc = mm::mappo_cent_check(d, a->obs, a->cent_obs, a->rows, "mappo_ff_fwd");
+  if (rc != MM_OK) return rc;
+#define MM_CALL(D, N) mm::mgr::roll_ff_fwd<D, 5, N>(a, (hipStream_t)s)
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  return mm::mappo_dims_error(d);
+}
+
+int64_t mm_mappo_ff_grad_scratch_count(const mm_mappo_dims* d) {
+  if (!d || !mm::mappo_dims_supported(d)) return -1;
+#define MM_CALL(D, N) mm::mgr::FfGradShape<D, 5, N>::scratch()
+  MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
+#undef MM_CALL
+  return -1;
+}
+
+int mm_mappo_ff_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const int32_t* rows, int64_t n_rows,
+                     float* grad_actor, float* grad_critic, float* scratch, mm_stream_t s) {
+  MM_REQUIRE(d && a && grad_actor && grad_critic && scratch, "mappo_ff_grad: null argument");
+  MM_REQUIRE(a->T > 0 && a->en > 0, "mappo_ff_grad: need T > 0 and en > 0");
+  MM_REQUIRE(!rows || (int64_t)a->T * a->en < (1ll << 31), "mappo_ff_grad: T * en must be below 2^31 with a row list");
+  MM_REQUIRE(!rows || (n_rows >= 1 && n_rows <= (int64_t)a->T * a->en), "mappo_ff_grad: need 1 <= n_rows <= T * en");
+  MM_REQUIRE(a->P[0] && a->P[1] && a->obs && a->active && a->act && a->adv && a->old_logp && a->old_value &&
+                 a->returns && a->stats,
+             "mappo_ff_grad: null pointer");
+  MM_REQUIRE(((uintptr_t)scratch & 15) == 0, "mappo_ff_grad: scratch must be 16-byte aligned");
+  if (!mm::mappo_dims_supported(d)) return mm::mappo_dims_error(d);
+  const int rc = mm::mappo_cent_check(d, a->obs, a->cent_obs, a->en, "mappo_ff_grad");
+  if (rc != MM_OK) return rc;
+#define MM_CALL(D, N) \
+  mm::mgr::FfGradShape<D, 5, N>::run(a, rows, n_rows, grad_actor, grad_critic, scratch, (hipStream_t)s)
   MM_MAPPO_GRAD_SHAPES(d, MM_CALL);
 #undef MM_CALL
   return mm::mappo_dims_error(d);

@@ -346,6 +346,10 @@ _SIGS += [
     ("mm_mappo_vn_update", c_i32, [c_vp, c_vp, c_f64, c_vp]),
     ("mm_mappo_stats_from_sums", c_i32, [c_vp, c_i64, c_vp, c_vp]),
     ("mm_mappo_insert", c_i32, [c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("mm_mappo_ff_fwd", c_i32, [_MD, ctypes.POINTER(MappoFwdArgs), c_vp]),
+    ("mm_mappo_ff_grad_scratch_count", c_i64, [_MD]),
+    ("mm_mappo_ff_grad", c_i32, [_MD, ctypes.POINTER(MappoBwdArgs), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    ("mm_mappo_ff_insert", c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
 ]
 
 

@@ -248,7 +248,12 @@ class R_MAPPOPolicy:
     """rmappo_policy.py:7-153 over the fused actor / critic kernels (shared policy, recurrent, Discrete).
 
     args.use_centralized_V with cent_obs_space.shape == (n * D,): the critic reads the explicit cent_obs the
-    caller passes (share_obs, base_runner.py:155-161), as in the reference's signatures."""
+    caller passes (share_obs, base_runner.py:155-161), as in the reference's signatures.
+
+    args.algorithm_name == "mappo", or args.use_recurrent_policy False without use_naive_recurrent_policy
+    (mappo/main.py:62-65, r_actor_critic.py:46,123): feed-forward nets (MappoPolicy(recurrent=False)). get_actions,
+    get_values and act keep their signatures and hand the rnn_states they were given back unchanged;
+    evaluate_actions is not built for them (it would need an entropy output of the feed-forward forward)."""
 
     def __init__(self, args, obs_space, cent_obs_space, act_space, device="cuda", seed=None):
         from .mappo import MappoPolicy
@@ -267,13 +272,17 @@ class R_MAPPOPolicy:
         self.actor_lr = float(getattr(args, "actor_lr", getattr(args, "lr", 1e-4)))
         self.critic_lr = float(getattr(args, "critic_lr", 1e-4))
         self.opti_eps = float(getattr(args, "opti_eps", 1e-5))
-        self.policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device, seed=seed, cent_agents=cent_agents)
+        self.recurrent = not (getattr(args, "algorithm_name", "rmappo") == "mappo" or
+                              (getattr(args, "use_recurrent_policy", True) is False and
+                               not getattr(args, "use_naive_recurrent_policy", False)))
+        self.policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device, seed=seed, cent_agents=cent_agents,
+                                  recurrent=self.recurrent)
         self.actor, self.critic = self.policy.actor, self.policy.critic
         self.cent_agents = cent_agents
         # evaluate_actions' actor half runs the decentralized TRAIN forward (both nets; its critic's values are
         # dropped): a decentralized policy whose actor storage is pointed at self.policy's on every call
         self._actor_policy = self.policy
-        if cent_agents:
+        if cent_agents and self.recurrent:
             self._actor_policy = MappoPolicy(D, int(act_space.n), self.hidden, self.device)
         self.seed = int(getattr(args, "seed", 1))
         self._counter = 0
@@ -300,6 +309,10 @@ class R_MAPPOPolicy:
         obs_t = self._t(obs)
         co = self._same_input(obs_t, cent_obs)
         R = obs_t.shape[0]
+        if not self.recurrent:
+            v, a, lp, _, _ = self.policy.get_actions(obs_t, seed=self.seed, counter=self._counter, cent_obs=co)
+            self._counter += 1
+            return v, a.long(), lp, rnn_states_actor, rnn_states_critic
         ha = self._t(rnn_states_actor).reshape(R, self.hidden)
         hc = self._t(rnn_states_critic).reshape(R, self.hidden)
         m = self._t(masks).reshape(R)
@@ -311,12 +324,25 @@ class R_MAPPOPolicy:
     def get_values(self, cent_obs, rnn_states_critic, masks):
         co = self._t(cent_obs)
         R = co.shape[0]
+        if not self.recurrent:
+            return self.policy.get_values(co)
         return self.policy.get_values(co, self._t(rnn_states_critic).reshape(R, self.hidden), self._t(masks).reshape(R))
 
     def act(self, obs, rnn_states_actor, masks, available_actions=None, deterministic=False):
         from ._lib import MM_MAPPO_ROLLOUT, MappoFwdArgs
         obs_t = self._t(obs)
         R = obs_t.shape[0]
+        if not self.recurrent:
+            lp, v = torch.empty(R, device=self.device), torch.empty(R, device=self.device)
+            act = torch.empty(R, dtype=torch.int32, device=self.device)
+            co = torch.zeros(R, self.policy.Dc, device=self.device) if self.cent_agents else None
+            a = self.policy.rollout_args(obs_t, logp_out=lp, value_out=v, act_out=act, seed=self.seed,
+                                         counter=self._counter, cent_obs=co)
+            a.mode = MM_MAPPO_ROLLOUT
+            a.deterministic = 1 if deterministic else 0
+            self._counter += 1
+            self.policy._fwd(a)
+            return act.long().view(R, 1), rnn_states_actor
         ha = self._t(rnn_states_actor).reshape(R, self.hidden)
         hc = torch.zeros_like(ha)
         ha2, hc2 = torch.empty_like(ha), torch.empty_like(ha)
@@ -340,6 +366,10 @@ class R_MAPPOPolicy:
         Centralized critic: the actor half as above; the values from L chained VALUES-mode forwards over the
         explicit cent_obs (hidden carried from step to step, h <- h * mask inside the kernel)."""
         from .mappo import MappoBuffer, MappoTrainer
+        if not self.recurrent:
+            raise NotImplementedError("evaluate_actions of a feed-forward policy (algorithm_name 'mappo') is not "
+                                      "built: the feed-forward forward (mm_mappo_ff_fwd) has no entropy output; "
+                                      "train through MappoTrainer instead")
         obs_t = self._t(obs)
         co = self._same_input(obs_t, cent_obs)
         rows = obs_t.shape[0]

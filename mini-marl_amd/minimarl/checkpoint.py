@@ -10,7 +10,8 @@ Supported components (``checkpoint_tensors()`` / ``restore_tensors()`` protocol)
   QLearner      behavior [agent | mixer] parameters, target agent / mixer, Adam m / v / step
   OffQMix       behavior + target [agent | mixer], Adam m / v / step
   MappoTrainer  actor / critic parameters, both Adam states, ValueNorm running statistics; scalar: the number of
-                train() calls (seeds the minibatch permutations; 0 when absent)
+                train() calls (seeds the minibatch permutations; 0 when absent) and the policy mode (recurrent 1 | 0;
+                recurrent when absent; loading across modes raises ValueError)
 """
 import json
 

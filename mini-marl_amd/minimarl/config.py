@@ -89,7 +89,8 @@ def qmix_reference():
 @dataclass
 class MappoTrainConfig:
     """mappo/_config.py values on the hot path (rmappo, shared policy, recurrent chunks; train_batch_size PPO
-    minibatches per epoch = MappoTrainer / MappoRunner num_mini_batch)."""
+    minibatches per epoch = MappoTrainer / MappoRunner num_mini_batch). algorithm_name "mappo" (mappo/main.py:62-65):
+    feed-forward nets and row minibatches, MappoPolicy(recurrent=False); data_chunk_length is then unused."""
     n_envs: int = 4096
     n_agents: int = 8
     episode_length: int = 100
@@ -110,6 +111,16 @@ class MappoTrainConfig:
     seed: int = 1
     # centralized critic over the env's share_obs (mappo/_config.py use_centralized_V; MappoPolicy(cent_agents=n_agents))
     use_centralized_V: bool = False
+    algorithm_name: str = "rmappo"     # "rmappo" | "mappo" (feed-forward, mappo/main.py:62-65)
+
+    def __post_init__(self):
+        if self.algorithm_name not in ("rmappo", "mappo"):
+            raise ValueError(f"algorithm_name={self.algorithm_name!r}: expected 'rmappo' or 'mappo'")
+
+    @property
+    def recurrent(self):
+        """The MappoPolicy(recurrent=...) argument of this configuration."""
+        return self.algorithm_name != "mappo"
 
 
 @dataclass

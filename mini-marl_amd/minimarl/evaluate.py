@@ -77,6 +77,16 @@ class MappoEvaluator:
         act = torch.empty(R, dtype=torch.int32, device=dev)
         active = torch.ones(E, dtype=torch.uint8, device=dev)
         score = torch.zeros(E, device=dev)
+        if not getattr(policy, "recurrent", True):   # feed-forward nets: no hiddens to carry
+            for _ in range(self.max_steps):
+                a = policy.rollout_args(obs, logp_out=lp, value_out=v, act_out=act)
+                a.mode, a.deterministic = MM_MAPPO_ROLLOUT, 1
+                policy._fwd(a)
+                nxt, rew, done = self.env.step(act.view(E, N))
+                check(lib().mm_eval_accum(E, N, 0.0, ptr(rew), ptr(done), None, None, ptr(active), ptr(score), None,
+                                          stream_handle(dev)), "eval_accum")
+                obs = nxt.reshape(R, -1).contiguous()
+            return float(score.mean()), score
         for _ in range(self.max_steps):
             a = policy.rollout_args(obs, ha, hc, None, ha2, hc2, lp, v, act_out=act)
             a.mode, a.deterministic = MM_MAPPO_ROLLOUT, 1

@@ -14,6 +14,9 @@ tests/test_mappo_oracle.py::test_ppo_train_golden[False]); with more, each epoch
 of the chunks and takes num_mini_batch steps on its slices, the remainder chunks dropped, as the
 reference's recurrent_generator does (shared_buffer.py:318-331) -- drawn by a device generator, since
 torch's CPU randperm stream is not the device's (a recorded one replays through train(perms=...)).
+Feed-forward nets (the reference's algorithm_name "mappo", main.py:62-65): MappoPolicy(recurrent=False); the buffer
+then holds no hidden states, the minibatches are slices of a permutation of the T * EN buffer rows
+(feed_forward_generator, shared_buffer.py:159-219) and the kernels are mm_mappo_ff_fwd / _ff_grad / _ff_insert.
 """
 import ctypes
 
@@ -37,6 +40,8 @@ REF_NAMES = {
     "bih": "rnn.rnn.bias_ih_l0", "bhh": "rnn.rnn.bias_hh_l0",
     "lnr_w": "rnn.norm.weight", "lnr_b": "rnn.norm.bias",
 }
+RECURRENT_KEYS = ("Wih", "Whh", "bih", "bhh", "lnr_w", "lnr_b")   # the RNNLayer's tensors (rnn.py)
+FF_KEYS = [k for k in KEYS if k not in RECURRENT_KEYS]
 HEAD_NAMES = {0: ("act.action_out.linear.weight", "act.action_out.linear.bias"), 1: ("v_out.weight", "v_out.bias")}
 
 
@@ -50,10 +55,16 @@ class MappoNet:
     """One net's parameters (net 0 = R_Actor, net 1 = R_Critic) in the kernel's flat layout.
 
     cent_agents n >= 2 (use_centralized_V): the critic's input is the env's share_obs, n obs rows wide; ``D`` is
-    the net's own input width (the critic's n * obs_dim), ``dims`` keeps the per-agent obs_dim."""
+    the net's own input width (the critic's n * obs_dim), ``dims`` keeps the per-agent obs_dim.
 
-    def __init__(self, net, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None):
+    recurrent=False (the reference's feed-forward nets, r_actor_critic.py:46,84,123,168,204): the same flat layout,
+    whose six RNNLayer tensors stay zero and are neither read, initialised, loaded nor exported."""
+
+    def __init__(self, net, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None,
+                 recurrent=True):
         self.net, self.A, self.H = int(net), int(n_actions), int(hidden)
+        self.recurrent = bool(recurrent)
+        self.keys = KEYS if self.recurrent else FF_KEYS
         self.cent_agents = int(cent_agents) if cent_agents and int(cent_agents) > 1 else None
         self.D = int(obs_dim) * (self.cent_agents if self.cent_agents and self.net == 1 else 1)
         self.O = self.A if self.net == 0 else 1
@@ -92,7 +103,7 @@ class MappoNet:
         g = torch.Generator().manual_seed(int(seed))
         self.flat.zero_()
         relu_gain = float(np.sqrt(2.0))
-        for key in KEYS:
+        for key in self.keys:
             shp = self.shape(key)
             if key.startswith("ln") and key.endswith("_w"):
                 self.view(key).fill_(1.0)
@@ -103,12 +114,12 @@ class MappoNet:
                 self.view(key).copy_(w.to(self.device))
 
     def load_reference_state(self, sd, prefix=""):
-        for k in KEYS:
+        for k in self.keys:
             v = torch.as_tensor(np.asarray(sd[prefix + ref_name(k, self.net)]), dtype=torch.float32)
             self.view(k).copy_(v.to(self.device))
 
     def state_dict(self):
-        return {ref_name(k, self.net): self.view(k).detach().cpu().clone() for k in KEYS}
+        return {ref_name(k, self.net): self.view(k).detach().cpu().clone() for k in self.keys}
 
 
 def _ptrs(*ts):
@@ -118,12 +129,18 @@ def _ptrs(*ts):
 class MappoPolicy:
     """R_MAPPOPolicy (rmappo_policy.py:7-153): shared actor + critic for all agents."""
 
-    def __init__(self, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None):
+    def __init__(self, obs_dim, n_actions=5, hidden=32, device="cuda", seed=None, cent_agents=None, recurrent=True):
         """cent_agents = n (use_centralized_V, base_runner.py:70-85): the critic reads the env's share_obs, the
-        concatenation of its n agents' obs rows (input width n * obs_dim); None: the row's own obs."""
-        self.actor = MappoNet(0, obs_dim, n_actions, hidden, device, None if seed is None else seed, cent_agents)
+        concatenation of its n agents' obs rows (input width n * obs_dim); None: the row's own obs.
+
+        recurrent=False: the reference's algorithm_name "mappo" (main.py:62-65), feed-forward nets without the
+        RNNLayer (mm_mappo_ff_fwd). get_actions / get_values / rollout_args then take None for the hiddens and masks
+        and hand back the hiddens they were given."""
+        self.recurrent = bool(recurrent)
+        self.actor = MappoNet(0, obs_dim, n_actions, hidden, device, None if seed is None else seed, cent_agents,
+                              self.recurrent)
         self.critic = MappoNet(1, obs_dim, n_actions, hidden, device, None if seed is None else seed + 1,
-                               cent_agents)
+                               cent_agents, self.recurrent)
         self.dims = self.actor.dims
         self.D, self.A, self.H = int(obs_dim), int(n_actions), int(hidden)
         self.cent_agents = self.actor.cent_agents
@@ -144,11 +161,16 @@ class MappoPolicy:
         return None, x
 
     def _fwd(self, args):
+        if not self.recurrent:
+            check(lib().mm_mappo_ff_fwd(ctypes.byref(self.dims), ctypes.byref(args), stream_handle(self.device)),
+                  "mappo_ff_fwd")
+            return
         check(lib().mm_mappo_fwd(ctypes.byref(self.dims), ctypes.byref(args), stream_handle(self.device)),
               "mappo_fwd")
 
-    def rollout_args(self, obs, ha, hc, masks, ha_out, hc_out, logp_out, value_out, act_out=None, act_in=None,
-                     u=None, seed=0, counter=0, counter_ptr=None, cent_obs=None):
+    def rollout_args(self, obs, ha=None, hc=None, masks=None, ha_out=None, hc_out=None, logp_out=None,
+                     value_out=None, act_out=None, act_in=None, u=None, seed=0, counter=0, counter_ptr=None,
+                     cent_obs=None):
         a = MappoFwdArgs()
         a.cent_obs = None if cent_obs is None else ptr(cent_obs)
         a.net[0].P, a.net[0].h_in, a.net[0].h_out, a.net[0].out = _ptrs(self.actor.flat, ha, ha_out, logp_out)
@@ -159,7 +181,7 @@ class MappoPolicy:
         a.mode = MM_MAPPO_ROLLOUT
         return a
 
-    def get_actions(self, obs, ha, hc, masks=None, actions=None, u=None, seed=0, counter=0, cent_obs=None):
+    def get_actions(self, obs, ha=None, hc=None, masks=None, actions=None, u=None, seed=0, counter=0, cent_obs=None):
         """obs [R,D], ha/hc [R,H], masks [R] -> values [R,1], actions [R,1], logp [R,1], ha', hc'.
 
         Centralized critic: cent_obs [R, n*D] is the reference's explicit critic input; None reads the share_obs
@@ -169,25 +191,35 @@ class MappoPolicy:
         to evaluate given actions (the reference's get_actions always samples, rmappo_policy.py:86)."""
         R = obs.shape[0]
         dev = self.device
-        ha2, hc2 = torch.empty(R, self.H, device=dev), torch.empty(R, self.H, device=dev)
+        if self.recurrent:
+            ha2, hc2 = torch.empty(R, self.H, device=dev), torch.empty(R, self.H, device=dev)
         lp, v = torch.empty(R, device=dev), torch.empty(R, device=dev)
         act_in = None if actions is None else actions.reshape(-1).to(torch.int32).contiguous()
         act = torch.empty(R, dtype=torch.int32, device=dev) if actions is None else act_in
         if cent_obs is not None:
             cent_obs = self._critic_input(cent_obs)[1]
+        if not self.recurrent:   # (the nets read neither hiddens nor masks; the hiddens pass through)
+            self._fwd(self.rollout_args(obs.contiguous(), None, None, None, None, None, lp, v,
+                                        None if actions is not None else act, act_in, u, seed, counter,
+                                        cent_obs=cent_obs))
+            return v.view(R, 1), act.view(R, 1), lp.view(R, 1), ha, hc
         self._fwd(self.rollout_args(obs.contiguous(), ha.contiguous(), hc.contiguous(),
                                     None if masks is None else masks.reshape(-1).contiguous(), ha2, hc2, lp, v,
                                     None if actions is not None else act, act_in, u, seed, counter,
                                     cent_obs=cent_obs))
         return v.view(R, 1), act.view(R, 1), lp.view(R, 1), ha2, hc2
 
-    def get_values(self, obs, hc, masks=None, hc_out=None):
+    def get_values(self, obs, hc=None, masks=None, hc_out=None):
         """obs: the critic's input, [R, D] (centralized: rows grouped by env) or an explicit cent_obs [R, n*D];
-        hc_out [R, H] (optional) receives the critic's new hidden."""
+        hc_out [R, H] (optional) receives the critic's new hidden (a feed-forward policy reads and writes none)."""
         R = obs.shape[0]
         v = torch.empty(R, device=self.device)
         a = MappoFwdArgs()
-        a.net[1].P, a.net[1].h_in, a.net[1].out, a.net[1].h_out = _ptrs(self.critic.flat, hc.contiguous(), v, hc_out)
+        if not self.recurrent:
+            hc = hc_out = masks = None
+        a.net[1].P, a.net[1].h_in, a.net[1].out, a.net[1].h_out = _ptrs(self.critic.flat,
+                                                                        None if hc is None else hc.contiguous(), v,
+                                                                        hc_out)
         o, co = self._critic_input(obs)
         # (the kernel's obs pointer is required; with an explicit cent_obs the critic does not read it)
         a.obs, a.cent_obs, a.mask = _ptrs(co if o is None else o, co,
@@ -204,14 +236,16 @@ def _rs(rows):
 class MappoBuffer:
     """SharedReplayBuffer (shared_buffer.py:15-129) in HBM: [T(+1), EN, ...] with EN = envs*agents."""
 
-    def __init__(self, T, n_envs, n_agents, obs_dim, hidden=32, device="cuda"):
+    def __init__(self, T, n_envs, n_agents, obs_dim, hidden=32, device="cuda", recurrent=True):
+        """recurrent=False (a feed-forward policy): no rnn_states / rnn_states_critic arrays (both None)."""
+        self.recurrent = bool(recurrent)
         self.T, self.E, self.N, self.D, self.H = int(T), int(n_envs), int(n_agents), int(obs_dim), int(hidden)
         self.EN = self.E * self.N
         dev = self.device = torch.device(device)
         T, EN = self.T, self.EN
         self.obs = torch.zeros(T + 1, EN, self.D, device=dev)
-        self.rnn_states = torch.zeros(T + 1, EN, self.H, device=dev)
-        self.rnn_states_critic = torch.zeros(T + 1, EN, self.H, device=dev)
+        self.rnn_states = torch.zeros(T + 1, EN, self.H, device=dev) if self.recurrent else None
+        self.rnn_states_critic = torch.zeros(T + 1, EN, self.H, device=dev) if self.recurrent else None
         self.value_preds = torch.zeros(T + 1, EN, device=dev)
         self.returns = torch.zeros(T + 1, EN, device=dev)
         self.actions = torch.zeros(T, EN, dtype=torch.int32, device=dev)
@@ -225,8 +259,9 @@ class MappoBuffer:
         def put(dst, src, dtype=torch.float32):
             dst.copy_(torch.as_tensor(np.ascontiguousarray(src)).reshape(dst.shape).to(dtype))
         put(self.obs, data["obs"])
-        put(self.rnn_states, data["rnn_states"])
-        put(self.rnn_states_critic, data["rnn_states_critic"])
+        if self.recurrent:
+            put(self.rnn_states, data["rnn_states"])
+            put(self.rnn_states_critic, data["rnn_states_critic"])
         put(self.value_preds, data["value_preds"])
         put(self.returns, data["returns"])
         put(self.actions, data["actions"], torch.int32)
@@ -238,7 +273,8 @@ class MappoBuffer:
     def after_update(self):
         """shared_buffer.py:119-129: last slot becomes the first."""
         for t in (self.obs, self.rnn_states, self.rnn_states_critic, self.masks, self.active_masks):
-            t[0].copy_(t[-1])
+            if t is not None:
+                t[0].copy_(t[-1])
 
     def compute_returns(self, vn, gamma=0.99, gae_lambda=0.95):
         """shared_buffer.py:131-153 with ValueNorm (value_preds[T] must hold the next value)."""
@@ -275,7 +311,22 @@ class MappoTrainer:
         M > 1 = per epoch one permutation of the T * EN / L chunks, M steps on its slices of
         (T * EN / L) // M chunks (mm_mappo_mb_stats + mm_mappo_vn_update + mm_mappo_grad_mb + mm_clip_adam each),
         the remainder dropped. perm_seed seeds the device generator of those permutations together with the
-        number of train() calls so far and the epoch."""
+        number of train() calls so far and the epoch.
+
+        A feed-forward policy (MappoPolicy(recurrent=False); feed_forward_generator, shared_buffer.py:159-219): L is
+        ignored and the unit of permutation is the buffer row t * EN + en (the reference numbers rows the same way):
+        n_chunks counts rows, a minibatch holds (T * EN) // M of them, perms is [epochs, T * EN]; one
+        mm_mappo_ff_grad per update."""
+        self.recurrent = bool(getattr(policy, "recurrent", True))
+        if not self.recurrent:
+            L = 1
+            if not fused:
+                raise NotImplementedError("fused=False with a feed-forward policy: only the fused gradient pass "
+                                          "(mm_mappo_ff_grad) exists for it, the saves + wgrad path is recurrent")
+            if int(num_mini_batch) > 1 and policy.cent_agents and policy.cent_agents >= 8:
+                raise NotImplementedError(f"num_mini_batch={num_mini_batch} with a feed-forward policy and cent_agents="
+                                          f"{policy.cent_agents}: mm_mappo_ff_grad refuses a row list for the "
+                                          f"{policy.Dc}-wide critic; use num_mini_batch=1")
         assert T % L == 0, "episode length must be a multiple of data_chunk_length"
         self.fused = bool(fused)
         self.M, self.perm_seed, self.train_calls = int(num_mini_batch), int(perm_seed), 0
@@ -291,6 +342,9 @@ class MappoTrainer:
                 raise NotImplementedError(f"num_mini_batch={self.M} with grad_allreduce: the per-minibatch statistics "
                                           "(active count, return moments) would need their own all-reduce")
             if self.mbs < 1:
+                if not self.recurrent:
+                    raise NotImplementedError(f"num_mini_batch={self.M} exceeds the {self.n_chunks} rows of the "
+                                              f"buffer (T={T} x EN={EN}): a minibatch would hold no row")
                 raise NotImplementedError(f"num_mini_batch={self.M} exceeds the {self.n_chunks} chunks of the buffer "
                                           f"(T={T} x EN={EN} / L={L}): a minibatch would hold no chunk")
         if not self.fused and policy.cent_agents:
@@ -310,7 +364,12 @@ class MappoTrainer:
         d = ctypes.byref(policy.dims)
         self.rows = self.T * self.EN
         self.rs = _rs(self.rows)
-        if self.fused:
+        if not self.recurrent:
+            n_scr = int(L_.mm_mappo_ff_grad_scratch_count(d))
+            if n_scr <= 0:
+                raise RuntimeError("mappo_ff_grad: unsupported dims for the feed-forward gradient pass")
+            self.gscr = torch.zeros(n_scr, device=dev)
+        elif self.fused:
             n_scr = int(L_.mm_mappo_grad_scratch_count(d, self.L, self.T, self.EN))
             if n_scr <= 0:
                 raise RuntimeError("mappo_grad: unsupported dims for the fused gradient pass")
@@ -342,10 +401,15 @@ class MappoTrainer:
             ts[f"m{n}"], ts[f"v{n}"], ts[f"step{n}"] = self.m[n], self.v[n], self.step[n]
         # (the number of train() calls seeds the minibatch permutations: a resumed run draws what the uninterrupted
         # run would have drawn)
-        return ts, {"train_calls": self.train_calls}
+        return ts, {"train_calls": self.train_calls, "recurrent": int(self.recurrent)}
 
     def restore_tensors(self, ts, scalars):
         from .checkpoint import copy_into
+        saved = bool((scalars or {}).get("recurrent", 1))   # (absent in older files: recurrent)
+        if saved != self.recurrent:
+            name = {True: "recurrent (rmappo)", False: "feed-forward (mappo)"}
+            raise ValueError(f"checkpoint of a {name[saved]} policy cannot be loaded into a {name[self.recurrent]} "
+                             "trainer: the nets differ (RNNLayer present or not)")
         if tuple(ts["critic"].shape) != tuple(self.p.critic.flat.shape):
             # (centralized vs decentralized critic: name the widths, not the flat parameter counts)
             c, H = self.p.critic, self.p.H
@@ -425,6 +489,10 @@ class MappoTrainer:
         weight-gradient reduction, ramppo_network.py:56-209)."""
         L_, s, d = lib(), stream_handle(self.device), ctypes.byref(self.p.dims)
         ba = ba or self.bwd_args(buf)
+        if not self.recurrent:
+            check(L_.mm_mappo_ff_grad(d, ctypes.byref(ba), None, 0, ptr(self.grad[0]), ptr(self.grad[1]),
+                                      ptr(self.gscr), s), "mappo_ff_grad")
+            return
         if self.fused:
             check(L_.mm_mappo_grad(d, ctypes.byref(ba), ptr(buf.rnn_states), ptr(buf.rnn_states_critic),
                                    ptr(self.grad[0]), ptr(self.grad[1]), ptr(self.gscr), s), "mappo_grad")
@@ -481,10 +549,13 @@ class MappoTrainer:
         want = np.arange(self.n_chunks)
         for ep in range(self.epochs):
             if not np.array_equal(np.sort(pm[ep].astype(np.int64)), want):
-                raise ValueError(f"perms[{ep}] is not a permutation of the {self.n_chunks} chunks")
+                raise ValueError(f"perms[{ep}] is not a permutation of the {self.n_chunks} "
+                                 f"{'chunks' if self.recurrent else 'rows'}")
         return self._to_native(torch.as_tensor(pm.astype(np.int64), device=self.device))
 
     def _to_native(self, perms):
+        if not self.recurrent:   # (rows: the reference's numbering is the buffer's)
+            return perms.to(torch.int32).contiguous()
         return chunks_ref_to_native(perms, self.T, self.L, self.EN).to(torch.int32).contiguous()
 
     def mb_stats(self, buf, chunks):
@@ -496,6 +567,11 @@ class MappoTrainer:
     def gradients_mb(self, buf, chunks, ba=None):
         """gradients() over the chunks of one minibatch (device int32, native numbering)."""
         ba = ba or self.bwd_args(buf)
+        if not self.recurrent:   # (chunks: the minibatch's buffer rows)
+            check(lib().mm_mappo_ff_grad(ctypes.byref(self.p.dims), ctypes.byref(ba), ptr(chunks), int(chunks.numel()),
+                                         ptr(self.grad[0]), ptr(self.grad[1]), ptr(self.gscr),
+                                         stream_handle(self.device)), "mappo_ff_grad")
+            return
         check(lib().mm_mappo_grad_mb(ctypes.byref(self.p.dims), ctypes.byref(ba), ptr(chunks), int(chunks.numel()),
                                      ptr(buf.rnn_states), ptr(buf.rnn_states_critic), ptr(self.grad[0]),
                                      ptr(self.grad[1]), ptr(self.gscr), stream_handle(self.device)), "mappo_grad_mb")
@@ -511,7 +587,8 @@ class MappoTrainer:
 
     def train(self, buf, perms=None):
         """R_MAPPO.train (ramppo_network.py:211-287). perms (num_mini_batch > 1 only): [epochs, n_chunks]
-        permutations in the reference's chunk numbering c = en * (T / L) + kc replacing the drawn ones."""
+        permutations in the reference's chunk numbering c = en * (T / L) + kc replacing the drawn ones (a
+        feed-forward policy: [epochs, T * EN] permutations of the buffer rows t * EN + en)."""
         if self.M == 1:
             if perms is not None:
                 raise ValueError("perms needs num_mini_batch > 1: one minibatch per epoch holds every chunk, in "
@@ -552,7 +629,8 @@ class MappoRunner:
         self.E, self.N, self.D = env.E, env.N, env.obs_dim
         self.T, self.gamma, self.gl = int(T), gamma, gae_lambda
         dev = self.device = policy.device
-        self.buf = MappoBuffer(T, self.E, self.N, self.D, policy.H, dev)
+        self.recurrent = bool(getattr(policy, "recurrent", True))
+        self.buf = MappoBuffer(T, self.E, self.N, self.D, policy.H, dev, recurrent=self.recurrent)
         self.trainer = MappoTrainer(policy, T, self.E * self.N, L, ppo_epoch, grad_allreduce=grad_allreduce,
                                     num_mini_batch=num_mini_batch, perm_seed=int(seed))
         self.seed = int(seed)
@@ -561,6 +639,11 @@ class MappoRunner:
         self.args = []
         b = self.buf
         for t in range(self.T):
+            if not self.recurrent:
+                self.args.append(policy.rollout_args(b.obs[t], logp_out=b.action_log_probs[t],
+                                                     value_out=b.value_preds[t], act_out=b.actions[t],
+                                                     seed=self.seed, counter_ptr=ptr(self.counter)))
+                continue
             a = policy.rollout_args(b.obs[t], b.rnn_states[t], b.rnn_states_critic[t], b.masks[t],
                                     b.rnn_states[t + 1], b.rnn_states_critic[t + 1], b.action_log_probs[t],
                                     b.value_preds[t], act_out=b.actions[t], seed=self.seed,
@@ -572,6 +655,13 @@ class MappoRunner:
 
     def collect_step(self, t):
         L_, s, b = lib(), stream_handle(self.device), self.buf
+        if not self.recurrent:
+            self.p._fwd(self.args[t])
+            check(L_.mm_env_step(self.env.handle(), ptr(b.actions[t]), None, ptr(b.obs[t + 1]),
+                                 ptr(b.rewards[t]), ptr(self.done), s), "env_step")
+            check(L_.mm_mappo_ff_insert(ptr(self.done), self.N, self.E, ptr(b.masks[t + 1]),
+                                        ptr(b.active_masks[t + 1]), ptr(self.counter), s), "mappo_ff_insert")
+            return
         check(L_.mm_mappo_fwd(ctypes.byref(self.p.dims), ctypes.byref(self.args[t]), s), "mappo_fwd")
         # no terminal obs needed (MAPPO bootstraps through masks): only the auto-reset current obs
         check(L_.mm_env_step(self.env.handle(), ptr(b.actions[t]), None, ptr(b.obs[t + 1]),
@@ -587,7 +677,8 @@ class MappoRunner:
     def compute(self):
         b = self.buf
         a = MappoFwdArgs()
-        a.net[1].P, a.net[1].h_in, a.net[1].out = _ptrs(self.p.critic.flat, b.rnn_states_critic[self.T],
+        a.net[1].P, a.net[1].h_in, a.net[1].out = _ptrs(self.p.critic.flat,
+                                                        b.rnn_states_critic[self.T] if self.recurrent else None,
                                                         b.value_preds[self.T])
         a.obs, a.mask = _ptrs(b.obs[self.T], b.masks[self.T])
         a.rows, a.mode = b.EN, MM_MAPPO_VALUES

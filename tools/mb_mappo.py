@@ -1,9 +1,11 @@
 """MAPPO phase timing at BASELINE config 3 (4096 envs x 8 agents, T=100, L=5, 15 PPO epochs).
 
 usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n] [--centralized-v] [--minibatches M]
+                                [--feed-forward]
 Prints one JSON line: ms per rollout step, per compute (values + GAE), per train() and per epoch (medians over the
 timed episodes; the first episode is warm-up). --centralized-v: the critic reads the env's share_obs.
 --minibatches M: M PPO minibatches per epoch (num_mini_batch; an epoch is then M updates on 1 / M of the chunks each).
+--feed-forward: the reference's algorithm_name "mappo" (nets without the GRU, minibatches over rows).
 """
 import argparse
 import json
@@ -29,9 +31,11 @@ def main():
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--centralized-v", action="store_true", help="centralized critic (use_centralized_V)")
     ap.add_argument("--minibatches", type=int, default=1, help="PPO minibatches per epoch (num_mini_batch)")
+    ap.add_argument("--feed-forward", action="store_true", help="feed-forward nets (algorithm_name mappo)")
     a = ap.parse_args()
     env = VecEnv(a.envs, a.agents, max_steps=100, device="cuda")
-    p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0, **({"cent_agents": a.agents} if a.centralized_v else {}))
+    p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0, **({"cent_agents": a.agents} if a.centralized_v else {}),
+                    **({"recurrent": False} if a.feed_forward else {}))
     r = MappoRunner(env, p, T=a.T, L=5, ppo_epoch=a.epochs, seed=1, num_mini_batch=a.minibatches)
     r.warmup()
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -53,7 +57,8 @@ def main():
     epi = med([sum(x) for x in res])   # (the median episode, not the sum of the phase medians)
     rows = a.envs * a.agents * a.T
     out = {"envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs, "centralized_v": bool(a.centralized_v),
-           "minibatches": a.minibatches, "train_ms_per_update": tr / (a.epochs * a.minibatches),
+           "minibatches": a.minibatches, "feed_forward": bool(a.feed_forward),
+           "train_ms_per_update": tr / (a.epochs * a.minibatches),
            "episodes": len(res),
            "rollout_ms_per_step": ro / a.T, "compute_ms": co, "train_ms": tr, "train_ms_per_epoch": tr / a.epochs,
            "episode_ms": epi, "agent_env_steps_per_s_incl_train": rows / (epi / 1e3),
