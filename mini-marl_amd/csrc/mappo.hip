@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mappo_loss.h"
 #include "minimarl.h"
 #include "trunk.h"
 
@@ -102,25 +103,6 @@ struct Trunk {
     matvec<O, H, H>(W + G::Wo, W + G::bo, f, out);
   }
 };
-
-// log-softmax in place (logits -> logp), returns entropy
-template <int A>
-__device__ __forceinline__ float log_softmax(float (&l)[A]) {
-  float mx = l[0];
-#pragma unroll
-  for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
-  float s = 0.0f;
-#pragma unroll
-  for (int a = 0; a < A; ++a) s += expf(l[a] - mx);
-  const float lse = mx + logf(s);
-  float ent = 0.0f;
-#pragma unroll
-  for (int a = 0; a < A; ++a) {
-    l[a] -= lse;
-    ent -= expf(l[a]) * l[a];
-  }
-  return ent;
-}
 
 // ------------------------------------------------------------------ forward kernel
 template <int D, int H, int A>
@@ -235,16 +217,6 @@ __global__ __launch_bounds__(256) void mappo_fwd_kernel(mm_mappo_fwd_args a) {
 // Per chunk, reverse over its L steps: loss seed (PPO clipped surrogate + entropy for the
 // actor, ValueNorm-targeted clipped Huber for the critic), then BPTT through head, LN_r, GRU,
 // LN2/L2, LN1/L1, LN0. Writes the (delta, input) operand pairs of every weight gradient.
-struct LossSeed {
-  float clip, huber_delta, entropy_coef, value_coef;
-};
-
-__device__ __forceinline__ float huber_d(float e, float d) { return fabsf(e) <= d ? e : (e > 0.f ? d : -d); }
-__device__ __forceinline__ float huber_f(float e, float d) {
-  return fabsf(e) <= d ? e * e * 0.5f : d * (fabsf(e) - d * 0.5f);
-}
-
-
 template <int D, int H, int A, int O>
 __device__ __forceinline__ void bwd_body(const mm_mappo_bwd_args& a, int net, const float* W) {
   using G = MGeo<D, H, O>;
@@ -274,42 +246,12 @@ __device__ __forceinline__ void bwd_body(const mm_mappo_bwd_args& a, int net, co
       float ent = 0.0f;
 #pragma unroll
       for (int q = 0; q < A; ++q) ent -= expf(lp[q]) * lp[q];
-      const int act = a.act[row];
-      float lpa = lp[0];
-#pragma unroll
-      for (int q = 1; q < A; ++q)
-        if (q == act) lpa = lp[q];
-      const float adv = (a.adv[row] - a.stats[MM_MST_ADV_MEAN]) / (a.stats[MM_MST_ADV_STD] + 1e-5f);
-      const float ratio = expf(lpa - a.old_logp[row]);
-      const float s1 = ratio * adv;
-      const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
-      const float s2 = rc * adv;
-      const float inr = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
-      // torch.min backward: the smaller side gets the gradient, ties split it in half
-      const float g = s1 < s2 ? 1.0f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
-      const float dlpa = -m * inv_m * adv * ratio * g;
-      const float dent = -a.entropy_coef * m * inv_m;
-      lsum0 += -fminf(s1, s2) * m;
-      lsum1 += ent * m;
-      lsum2 += ratio;
-#pragma unroll
-      for (int q = 0; q < A; ++q) {
-        const float p = expf(lp[q]);
-        dout[q] = dlpa * ((q == act ? 1.0f : 0.0f) - p) + dent * (-p * (lp[q] + ent));
-      }
+      const PolicyTerms lt = policy_seed<A>(a, row, m, inv_m, lp, ent, dout);
+      lsum0 += lt.loss;
+      lsum1 += lt.ent;
+      lsum2 += lt.ratio;
     } else {
-      const float v = soa_ld1(sv, S::OUT);
-      const float old = a.old_value[row];
-      const float tgt = (a.returns[row] - a.stats[MM_MST_VN_MEAN]) / a.stats[MM_MST_VN_STD];
-      const float dv = v - old;
-      const float vc = old + fminf(fmaxf(dv, -a.clip), a.clip);
-      const float eo = tgt - v, ec = tgt - vc;
-      const float lo = huber_f(eo, a.huber_delta), lc = huber_f(ec, a.huber_delta);
-      const float go_ = -huber_d(eo, a.huber_delta);
-      const float gc = -huber_d(ec, a.huber_delta) * ((dv >= -a.clip && dv <= a.clip) ? 1.0f : 0.0f);
-      const float d = lo > lc ? go_ : (lc > lo ? gc : 0.5f * (go_ + gc));
-      dout[0] = a.value_coef * m * inv_m * d;
-      lsum0 += fmaxf(lo, lc) * m;
+      lsum0 += value_seed(a, row, m, inv_m, soa_ld1(sv, S::OUT), dout[0]);
     }
     // ---- head: y = LN_r(h2); out = Wo y + bo
     float xr[H], t[H];
@@ -436,24 +378,7 @@ __device__ __forceinline__ void bwd_body(const mm_mappo_bwd_args& a, int net, co
       soa_st<D>(go, GF_::F0, x0);
     }
   }
-  if (a.loss_acc) {
-    // logging only (train_info): wave-level sums, one atomic per wave
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lsum0 += __shfl_xor(lsum0, o);
-      lsum1 += __shfl_xor(lsum1, o);
-      lsum2 += __shfl_xor(lsum2, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      if constexpr (O == A) {
-        atomicAdd(&a.loss_acc[MM_MLOSS_POLICY], lsum0 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_ENTROPY], lsum1 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_RATIO], lsum2);
-      } else {
-        atomicAdd(&a.loss_acc[MM_MLOSS_VALUE], lsum0 * inv_m);
-      }
-    }
-  }
+  loss_flush<O == A>(a.loss_acc, lsum0, lsum1, lsum2, inv_m);
 }
 
 template <int D, int H, int A>

@@ -32,11 +32,14 @@
 // Minibatch variant (mm_mappo_grad_mb, the *_mb kernels): the same two bodies with IDX = true run over a list of
 // chunks (one PPO minibatch of recurrent_generator's sampler) instead of all of them.
 // Feed-forward nets (algorithm_name "mappo": no GRU, no LN_r; mm_mappo_ff_fwd / mm_mappo_ff_grad, at the end of the
-// namespace): a rollout forward without the recurrent part and one row-parallel gradient pass, pass M's body with
-// the head and the loss seed in registers, over all rows or a row list.
+// namespace): a rollout forward without the recurrent part and one row-parallel gradient pass, pass M's backward
+// (MlpBwd) fed by a head and loss seed in registers, over all rows or a row list.
+// The per-row loss arithmetic (log-softmax, PPO / Huber seeds, the logged loss sums) is mappo_loss.h's, shared with
+// mappo.hip's per-thread backward.
 #include <algorithm>
 
 #include "common.h"
+#include "mappo_loss.h"
 #include "minimarl.h"
 #include "trunk.h"
 
@@ -189,6 +192,20 @@ __device__ __forceinline__ void ln32_bwd(const float (&dy)[16], const float (&xh
   sgx = xsum(sgx) / 32.f;
 #pragma unroll
   for (int q = 0; q < 16; ++q) dx[q] = rs * (dy[q] * w[kperm(q, h)] - sg - xh[q] * sgx);
+}
+
+// head: out[o] = bo[o] + sum_i Wo[o][i] y[i] of an act-frag vector y (Wo: LDS rows of 32; both lane halves get it).
+// h: the caller's lane half (lane_h() here instead costs pass G two spilled VGPRs at D 94)
+template <int O>
+__device__ __forceinline__ void head_out(const float* Wo, const float* bo, const float (&y)[16], float (&out)[O],
+                                         int h) {
+#pragma unroll
+  for (int o = 0; o < O; ++o) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s = fmaf(Wo[o * 32 + kperm(q, h)], y[q], s);
+    out[o] = bo[o] + xsum(s);
+  }
 }
 
 // value of LDS image offset e (< Geo::scr) from the net's flat MGeo parameters
@@ -897,7 +914,9 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm, const int32_t* _
         for (int q = 0; q < 16; ++q) s = fmaf(smb[GH::Wo + o * 32 + kperm(q, h)], y[q], s);
         out[o] = smb[GH::bo + o] + xsum(s);
       }
-      // ---- loss seed d(out) (mappo.hip bwd_body; ramppo_network.py:56-209)
+      // ---- loss seed d(out): log_softmax + policy_seed / value_seed of mappo_loss.h, and head_out above, spelled out.
+      // With the calls this pass has fewer spills (21 -> 12 VGPRs at D 47) and is 2.3 % slower (4.29 -> 4.39 ms per
+      // cfg3 epoch, measured); this text compiles to the code the timings in DESIGN.md were taken with.
       const float m = valid ? a.active[row] : 0.f;
       float dout[O];
       if constexpr (O == A) {
@@ -1123,24 +1142,7 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm, const int32_t* _
     }
   }
 
-  // ---- loss sums (logging only, train_info): one atomic per wave
-  if (a.loss_acc) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lsum0 += __shfl_xor(lsum0, o);
-      lsum1 += __shfl_xor(lsum1, o);
-      lsum2 += __shfl_xor(lsum2, o);
-    }
-    if (lane == 0) {
-      if constexpr (O == A) {
-        atomicAdd(&a.loss_acc[MM_MLOSS_POLICY], lsum0 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_ENTROPY], lsum1 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_RATIO], lsum2);
-      } else {
-        atomicAdd(&a.loss_acc[MM_MLOSS_VALUE], lsum0 * inv_m);
-      }
-    }
-  }
+  loss_flush<O == A>(a.loss_acc, lsum0, lsum1, lsum2, inv_m);
 
   // ---- block reduction of the waves (fixed order) into the flat gradient layout, one partial
   __syncthreads();
@@ -1183,6 +1185,190 @@ __device__ void gru_body(const GradArgs& k, int net, float* sm, const int32_t* _
   float* outp = k.partial + ((int64_t)net * 2 * NB + blockIdx.x) * k.pstride;
   for (int e = threadIdx.x; e < F::total; e += blockDim.x) outp[e] = red[e];
 }
+
+// Pass M's backward of one net for one wave: the weight-gradient accumulators and column sums (kept in registers over
+// the wave's tiles), the per-tile backward from d x2 and the fold into the block's reduction image. ffg_body feeds it
+// the d x2 of its own head. mlp_body (pass G's d x2) still holds this text inline: through the struct its resource
+// report is equal or better at every shape, but the 8-agent centralized epoch measured 1 % slower (11.64 -> 11.75 ms).
+template <int D, int O, bool WIDE>
+struct MlpBwd {
+  using GM = GeoM<D, O>;
+  using F = MGeo<D, H, O>;
+  using LO = LnOff<D>;
+  static constexpr int DT = GM::DT;
+  f32x16 aW2, aW1[DT];
+  float sb2, sb1, sl2w, sl2b, sl1w, sl1b, sl0w[DT], sl0b[DT];
+
+  __device__ __forceinline__ void init() {
+    zero16(aW2);
+#pragma unroll
+    for (int t = 0; t < DT; ++t) zero16(aW1[t]);
+    sb2 = sb1 = sl2w = sl2b = sl1w = sl1b = 0.f;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) sl0w[t] = sl0b[t] = 0.f;
+  }
+  // One tile of 32 rows: mp = the rows' forward on the image smb, orow / dxv = the lane's input row and d x2 (zero on a
+  // tail lane), S0..S2 = the wave's transpose tiles. lv (the image's LayerNorm / bias vectors) and the scales sw / s_f0
+  // / s_f1 are loaded by the caller before the forward: loaded here, the 376-wide critic spills 10 to 15 more VGPRs.
+  __device__ __forceinline__ void tile(const float* smb, const float* lv, float sw, float s_f0, float s_f1,
+                                       const MlpH<D, GM, WIDE>& mp, const float* __restrict__ orow,
+                                       const float (&dxv)[16], float* S0, float* S1, float* S2, int h) {
+    // ---- LN2 backward (x2 = LN2(a2), a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
+    float da[16], xh[16], tt[16], f1[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) xh[q] = (mp.a2[q] - mp.mu2) * mp.rs2;
+    ln32_bwd(dxv, xh, mp.rs2, lv + LO::ln2w, da);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      tt[q] = dxv[q] * xh[q];
+      da[q] = mp.a2[q] > 0.f ? da[q] : 0.f;
+      xh[q] = (mp.a1[q] - mp.mu1) * mp.rs1;
+      f1[q] = xh[q] * lv[LO::ln1w + kperm(q, h)] + lv[LO::ln1b + kperm(q, h)];
+    }
+    tput(S0, da);
+    tput(S1, f1);
+    tput(S2, tt);
+    const float s_a2 = scale_for(wave_max(absmax16(da)));
+    // ---- LN1 backward: dx1 = W2^T da2 (one scale per column), then da1
+    float dx1[16], da1[16];
+    {
+      const float c_a = scale_for(col_max(absmax16(da)));
+      S16 sa;
+      split16s(da, c_a, sa);
+      f32x16 acc;
+      zero16(acc);
+      mmh(smb + GM::W2T, sa, acc);
+      const float u = 1.0f / (sw * c_a);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dx1[q] = acc[q] * u;
+      ln32_bwd(dx1, xh, mp.rs1, lv + LO::ln1w, da1);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        tt[q] = dx1[q] * xh[q];
+        da1[q] = mp.a1[q] > 0.f ? da1[q] : 0.f;
+      }
+    }
+    wave_fence();
+    // dW2 += da2 f1^T, db2
+    float At[16];
+    {
+      float Bt[16];
+      tget(S0, At);
+      tget(S1, Bt);
+      sl2w += tsum(S2);
+      wave_fence();
+      tput(S0, da1);
+      tput(S1, dxv);
+      tput(S2, tt);
+      S16 sa, sb;
+      split16s(At, s_a2, sa);
+      split16s(Bt, s_f1, sb);
+      f32x16 tmp;
+      zero16(tmp);
+      accg(tmp, sa, sb);
+      acc_unscale(aW2, tmp, 1.0f / (s_a2 * s_f1));
+#pragma unroll
+      for (int s = 0; s < 16; ++s) sb2 += At[s];
+    }
+    const float s_a1 = scale_for(wave_max(absmax16(da1)));
+    wave_fence();
+    sl2b += tsum(S1);
+    sl1w += tsum(S2);
+    tget(S0, At);   // da1 transposed
+    wave_fence();
+    tput(S1, dx1);
+    wave_fence();
+    sl1b += tsum(S1);
+    wave_fence();
+    // ---- L1 / LN0: dW1 += da1 f0^T, db1, df0 = W1^T da1 -> LN0 parameter gradients
+    {
+      S16 sa;
+      split16s(At, s_a1, sa);
+#pragma unroll
+      for (int s = 0; s < 16; ++s) sb1 += At[s];
+      const float c_b = scale_for(col_max(absmax16(da1)));
+      S16 sd;
+      split16s(da1, c_b, sd);
+      const float u_b = 1.0f / (sw * c_b), u_w = 1.0f / (s_a1 * s_f0);
+      float x[WIDE ? 1 : DT][16];
+      if constexpr (!WIDE) load_obs<D, DT>(orow, x);
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        float x0[16], f0[16], dfv[16];
+        if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);   // (streamed again: the wide row is not kept)
+        const float (&xt)[16] = x[WIDE ? 0 : t];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int f = 32 * t + kperm(q, h);
+          x0[q] = (xt[q] - mp.mu0) * mp.rs0;
+          f0[q] = x0[q] * lv[LO::ln0w + f] + lv[LO::ln0b + f];
+        }
+        tput(S0, f0);
+        f32x16 acc;
+        zero16(acc);
+        mmh(smb + GM::W1T + t * HBLK, sd, acc);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          dfv[q] = acc[q] * u_b;
+          tt[q] = dfv[q] * x0[q];
+        }
+        tput(S1, tt);
+        tput(S2, dfv);
+        wave_fence();
+        float Bt[16];
+        tget(S0, Bt);
+        sl0w[t] += tsum(S1);
+        sl0b[t] += tsum(S2);
+        S16 sb;
+        split16s(Bt, s_f0, sb);
+        f32x16 tmp;
+        zero16(tmp);
+        accg(tmp, sa, sb);
+        acc_unscale(aW1[t], tmp, u_w);
+        wave_fence();
+      }
+    }
+  }
+  // both lane halves' column sums
+  __device__ __forceinline__ void fold() {
+    sb2 = xsum(sb2);
+    sb1 = xsum(sb1);
+    sl2w = xsum(sl2w);
+    sl2b = xsum(sl2b);
+    sl1w = xsum(sl1w);
+    sl1b = xsum(sl1b);
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+      sl0w[t] = xsum(sl0w[t]);
+      sl0b[t] = xsum(sl0b[t]);
+    }
+  }
+  // this wave's sums added into the flat gradient layout at red (the caller orders the waves)
+  __device__ __forceinline__ void add(float* red, int ci, int h) const {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int mm = kperm(q, h);
+      red[F::W2 + mm * H + ci] += aW2[q];
+#pragma unroll
+      for (int t = 0; t < DT; ++t)
+        if (32 * t + ci < D) red[F::W1 + mm * F::Dp + 32 * t + ci] += aW1[t][q];
+    }
+    if (h == 0) {
+      red[F::b2 + ci] += sb2;
+      red[F::b1 + ci] += sb1;
+      red[F::ln2_w + ci] += sl2w;
+      red[F::ln2_b + ci] += sl2b;
+      red[F::ln1_w + ci] += sl1w;
+      red[F::ln1_b + ci] += sl1b;
+#pragma unroll
+      for (int t = 0; t < DT; ++t)
+        if (32 * t + ci < D) {
+          red[F::ln0_w + 32 * t + ci] += sl0w[t];
+          red[F::ln0_b + 32 * t + ci] += sl0b[t];
+        }
+    }
+  }
+};
 
 // ---------------------------------------------------------------- pass M: LN-MLP backward, row-parallel
 // One wave = 32 row-steps (rows on the MFMA's N), fp16x3 products on pass M's split image: the forward (MlpH), then
@@ -1242,7 +1428,8 @@ __device__ void mlp_body(const GradArgs& k, int net, float* sm, const int32_t* _
     const float* __restrict__ orow = in_row<D, NA>(a.obs, a.cent_obs, row);
     MlpH<D, GM, WIDE> mp;
     mp.run(smb, orow);
-    // ---- LN2 backward (x2 = LN2(a2), a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
+    // ---- from here MlpBwd::tile's text (see there why it is not called): LN2 backward (x2 = LN2(a2),
+    // a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
     float da[16], xh[16], tt[16], f1[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) xh[q] = (mp.a2[q] - mp.mu2) * mp.rs2;
@@ -1425,6 +1612,47 @@ __device__ void stage_fwd(float* sm, const float* __restrict__ P) {
   __syncthreads();
 }
 
+// One rollout row's output from its head outputs l: the value (O = 1), or the Categorical's action (given, the mode or
+// the inverse-CDF sample of the injected or counter-RNG uniform: mappo.hip fwd_body's arithmetic) and its log-prob
+template <int O>
+__device__ __forceinline__ void roll_row_out(const mm_mappo_fwd_args& a, const mm_mappo_net_io& io, uint64_t ctr,
+                                             int64_t row, float (&l)[O]) {
+  if constexpr (O == 1) {
+    if (io.out) io.out[row] = l[0];
+  } else {
+    log_softmax<O>(l);
+    int act;
+    if (a.act_in) {
+      act = a.act_in[row];
+    } else if (a.deterministic) {
+      act = 0;   // Categorical.mode() = first argmax (distributions.py:61-62)
+#pragma unroll
+      for (int q = 1; q < O; ++q)
+        if (l[q] > l[act]) act = q;
+      if (a.act_out) a.act_out[row] = act;
+    } else {
+      const float u = a.u ? a.u[row] : rng_uniform(rng_draw(a.seed, ctr, (uint64_t)row, 0x9E37ull));
+      act = O - 1;   // inverse CDF: first k with u < cumsum(p)[k], the last action if rounding leaves none
+      bool found = false;
+      float cs = 0.0f;
+#pragma unroll
+      for (int q = 0; q < O; ++q) {
+        cs += expf(l[q]);
+        if (!found && u < cs) {
+          act = q;
+          found = true;
+        }
+      }
+      if (a.act_out) a.act_out[row] = act;
+    }
+    float lp = l[0];
+#pragma unroll
+    for (int q = 1; q < O; ++q)
+      if (q == act) lp = l[q];
+    if (io.out) io.out[row] = lp;
+  }
+}
+
 template <int D, int A, int O, int NA = 1>
 __device__ void roll_body(const mm_mappo_fwd_args& a, int net, float* sm) {
   using G = Geo<D, O>;
@@ -1458,57 +1686,9 @@ __device__ void roll_body(const mm_mappo_fwd_args& a, int net, float* sm) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) y[q] = (gr.h2[q] - mur) * rsr * smo[G::lnrw + kperm(q, h)] + smo[G::lnrb + kperm(q, h)];
     float l[O];
-#pragma unroll
-    for (int o = 0; o < O; ++o) {
-      float sacc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sacc = fmaf(smo[G::Wo + o * 32 + kperm(q, h)], y[q], sacc);
-      l[o] = smo[G::bo + o] + xsum(sacc);
-    }
+    head_out<O>(smo + G::Wo, smo + G::bo, y, l, h);
     if (!valid || h != 0) continue;
-    if constexpr (O == 1) {
-      if (io.out) io.out[row] = l[0];
-    } else {
-      // log-softmax (mappo.hip log_softmax)
-      float mx = l[0];
-#pragma unroll
-      for (int q = 1; q < O; ++q) mx = fmaxf(mx, l[q]);
-      float se = 0.0f;
-#pragma unroll
-      for (int q = 0; q < O; ++q) se += expf(l[q] - mx);
-      const float lse = mx + logf(se);
-#pragma unroll
-      for (int q = 0; q < O; ++q) l[q] -= lse;
-      int act;
-      if (a.act_in) {
-        act = a.act_in[row];
-      } else if (a.deterministic) {
-        act = 0;   // Categorical.mode() = first argmax (distributions.py:61-62)
-#pragma unroll
-        for (int q = 1; q < O; ++q)
-          if (l[q] > l[act]) act = q;
-        if (a.act_out) a.act_out[row] = act;
-      } else {
-        const float u = a.u ? a.u[row] : rng_uniform(rng_draw(a.seed, ctr, (uint64_t)row, 0x9E37ull));
-        act = O - 1;   // inverse CDF: first k with u < cumsum(p)[k], the last action if rounding leaves none
-        bool found = false;
-        float cs = 0.0f;
-#pragma unroll
-        for (int q = 0; q < O; ++q) {
-          cs += expf(l[q]);
-          if (!found && u < cs) {
-            act = q;
-            found = true;
-          }
-        }
-        if (a.act_out) a.act_out[row] = act;
-      }
-      float lp = l[0];
-#pragma unroll
-      for (int q = 1; q < O; ++q)
-        if (q == act) lp = l[q];
-      if (io.out) io.out[row] = lp;
-    }
+    roll_row_out<O>(a, io, ctr, row, l);
   }
 }
 
@@ -1686,9 +1866,10 @@ struct GradShape {
 // post-GRU LayerNorm (rnn.py:79 belongs to the RNNLayer); hiddens and masks are never read. The flat parameter
 // layout stays MGeo's 18 tensors; the six recurrent ones are not read and get exactly zero gradient.
 //
-// Rollout / values forward (mappo_ff_roll_kernel): roll_body without the h_in load, the Gru and LN_r; the same
-// exact-f32 v_mfma_f32_32x32x2_f32 trunk (Mlp), 4 waves per block, blockIdx.y = net. Its LDS image holds the MLP
-// rows at Geo's offsets (Mlp reads them there), then the MLP's vectors (LnOff) and the head.
+// Rollout / values forward (mappo_ff_roll_kernel): roll_body without the h_in load, the Gru and LN_r (head_out and
+// roll_row_out are shared); the same exact-f32 v_mfma_f32_32x32x2_f32 trunk (Mlp), 4 waves per block, blockIdx.y =
+// net. Its LDS image holds the MLP rows at Geo's offsets (Mlp reads them there), then the MLP's vectors (LnOff) and
+// the head.
 template <int D, int O>
 struct GeoF {
   using G = Geo<D, O>;
@@ -1733,57 +1914,9 @@ __device__ void roll_ff_body(const mm_mappo_fwd_args& a, int net, float* sm) {
     }
     // head on x2: Wo x2 + bo
     float l[O];
-#pragma unroll
-    for (int o = 0; o < O; ++o) {
-      float sacc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sacc = fmaf(smo[GF::Wo + o * 32 + kperm(q, h)], x2[q], sacc);
-      l[o] = smo[GF::bo + o] + xsum(sacc);
-    }
+    head_out<O>(smo + GF::Wo, smo + GF::bo, x2, l, h);
     if (!valid || h != 0) continue;
-    if constexpr (O == 1) {
-      if (io.out) io.out[row] = l[0];
-    } else {
-      // log-softmax, then the given action, the mode or the inverse-CDF sample (roll_body's arithmetic)
-      float mx = l[0];
-#pragma unroll
-      for (int q = 1; q < O; ++q) mx = fmaxf(mx, l[q]);
-      float se = 0.0f;
-#pragma unroll
-      for (int q = 0; q < O; ++q) se += expf(l[q] - mx);
-      const float lse = mx + logf(se);
-#pragma unroll
-      for (int q = 0; q < O; ++q) l[q] -= lse;
-      int act;
-      if (a.act_in) {
-        act = a.act_in[row];
-      } else if (a.deterministic) {
-        act = 0;   // Categorical.mode() = first argmax (distributions.py:61-62)
-#pragma unroll
-        for (int q = 1; q < O; ++q)
-          if (l[q] > l[act]) act = q;
-        if (a.act_out) a.act_out[row] = act;
-      } else {
-        const float u = a.u ? a.u[row] : rng_uniform(rng_draw(a.seed, ctr, (uint64_t)row, 0x9E37ull));
-        act = O - 1;   // inverse CDF: first k with u < cumsum(p)[k], the last action if rounding leaves none
-        bool found = false;
-        float cs = 0.0f;
-#pragma unroll
-        for (int q = 0; q < O; ++q) {
-          cs += expf(l[q]);
-          if (!found && u < cs) {
-            act = q;
-            found = true;
-          }
-        }
-        if (a.act_out) a.act_out[row] = act;
-      }
-      float lp = l[0];
-#pragma unroll
-      for (int q = 1; q < O; ++q)
-        if (q == act) lp = l[q];
-      if (io.out) io.out[row] = lp;
-    }
+    roll_row_out<O>(a, io, ctr, row, l);
   }
 }
 
@@ -1821,11 +1954,11 @@ static int roll_ff_fwd(const mm_mappo_fwd_args* a, hipStream_t s) {
   return MM_OK;
 }
 
-// Gradient pass (mappo_ff_grad_kernel, one launch per update, row-parallel): pass M's body with the head in
-// registers in place of the d x2 load. Per tile of 32 rows: the LN-MLP forward on pass M's split image (MlpH, fp16x3
-// products), the logits / value from the recomputed x2 (fp32 FMAs: the head is at most 5 wide), the row's PPO / Huber
-// loss seed (gru_body's arithmetic on stats[ADV_MEAN / ADV_STD / ACTIVE_SUM / VN_MEAN / VN_STD]), dWo += dout x2^T
-// and dbo, d x2 = Wo^T dout, and from there pass M unchanged. No d x2 scratch, no parked activations. Image: GeoM's
+// Gradient pass (mappo_ff_grad_kernel, one launch per update, row-parallel): pass M with a head in registers in place
+// of the d x2 load. Per tile of 32 rows: the LN-MLP forward on pass M's split image (MlpH, fp16x3 products), the
+// logits / value from the recomputed x2 (fp32 FMAs: the head is at most 5 wide), the row's PPO / Huber loss seed
+// (mappo_loss.h, on stats[ADV_MEAN / ADV_STD / ACTIVE_SUM / VN_MEAN / VN_STD]), dWo += dout x2^T and dbo,
+// d x2 = Wo^T dout, and from there MlpBwd's tile. No d x2 scratch, no parked activations. Image: GeoM's
 // (stage_h<.., true>), then the f32 head, then the wave transpose tiles.
 // IDX: tile t's lane ci handles buffer row rows[32 t + ci] of a list of n_rows (one PPO minibatch of
 // feed_forward_generator, shared_buffer.py:159-219) instead of row 32 t + ci of all T EN; the list 0 .. T EN - 1
@@ -1864,7 +1997,6 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
   constexpr bool WIDE = NA > 1;
   using F = MGeo<D, H, O>;
   using LO = LnOff<D>;
-  constexpr int DT = GM::DT;
   const mm_mappo_bwd_args& a = k.a;
   stage_h<D, O, true>(sm, a.P[net]);
   for (int e = threadIdx.x; e < 8 * 32 + 8; e += blockDim.x) sm[GF::Wo + e] = stage_value<D, O>(a.P[net], Geo<D, O>::Wo + e);
@@ -1878,13 +2010,8 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
   const int wg = blockIdx.x * MWV + w, nwg = gridDim.x * MWV;
   const float inv_m = 1.0f / a.stats[MM_MST_ACTIVE_SUM];
 
-  f32x16 aW2, aW1[DT];
-  zero16(aW2);
-#pragma unroll
-  for (int t = 0; t < DT; ++t) zero16(aW1[t]);
-  float sb2 = 0.f, sb1 = 0.f, sl2w = 0.f, sl2b = 0.f, sl1w = 0.f, sl1b = 0.f, sl0w[DT], sl0b[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t) sl0w[t] = sl0b[t] = 0.f;
+  MlpBwd<D, O, WIDE> mb;
+  mb.init();
   // head: lane (i, h) sums dWo[o][i] over the rows 2 s + h of its tiles; lane c (h = 0) sums dbo over its rows
   float aWo[O], sbo[O];
 #pragma unroll
@@ -1913,6 +2040,8 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
       for (int q = 0; q < 16; ++q)
         x2[q] = (mp.a2[q] - mp.mu2) * mp.rs2 * smh[GM::ln0w + LO::ln2w + kperm(q, h)] +
                 smh[GM::ln0w + LO::ln2b + kperm(q, h)];
+      // (head_out's arithmetic, spelled out: with the call, in any form tried, the 376-wide critic's all-rows build
+      // spills 40 VGPRs instead of 7)
       float out[O];
 #pragma unroll
       for (int o = 0; o < O; ++o) {
@@ -1921,63 +2050,19 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
         for (int q = 0; q < 16; ++q) s = fmaf(smh[GF::Wo + o * 32 + kperm(q, h)], x2[q], s);
         out[o] = smh[GF::bo + o] + xsum(s);
       }
-      // ---- loss seed d(out) (gru_body's; ramppo_network.py:56-209)
+      // ---- loss seed d(out); the logging terms by selects, not a divergent region
       const float m = valid ? a.active[row] : 0.f;
+      const bool cnt = h == 0 && valid;
       float dout[O];
       if constexpr (O == A) {
-        float mx = out[0];
-#pragma unroll
-        for (int q = 1; q < A; ++q) mx = fmaxf(mx, out[q]);
-        float se = 0.f;
-#pragma unroll
-        for (int q = 0; q < A; ++q) se += expf(out[q] - mx);
-        const float lse = mx + logf(se);
-        float lp[A], ent = 0.f;
-#pragma unroll
-        for (int q = 0; q < A; ++q) {
-          lp[q] = out[q] - lse;
-          ent -= expf(lp[q]) * lp[q];
-        }
-        const int act = a.act[row];
-        float lpa = lp[0];
-#pragma unroll
-        for (int q = 1; q < A; ++q)
-          if (q == act) lpa = lp[q];
-        const float adv = (a.adv[row] - a.stats[MM_MST_ADV_MEAN]) / (a.stats[MM_MST_ADV_STD] + 1e-5f);
-        const float ratio = expf(lpa - a.old_logp[row]);
-        const float s1 = ratio * adv;
-        const float rc = fminf(fmaxf(ratio, 1.0f - a.clip), 1.0f + a.clip);
-        const float s2 = rc * adv;
-        const float inr = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
-        // torch.min backward: the smaller side gets the gradient, ties split it in half
-        const float g = s1 < s2 ? 1.0f : (s1 > s2 ? inr : 0.5f + 0.5f * inr);
-        const float dlpa = -m * inv_m * adv * ratio * g;
-        const float dent = -a.entropy_coef * m * inv_m;
-        const bool cnt = h == 0 && valid;   // (selects, not a divergent region)
-        lsum0 += cnt ? -fminf(s1, s2) * m : 0.f;
-        lsum1 += cnt ? ent * m : 0.f;
-        lsum2 += cnt ? ratio : 0.f;
-#pragma unroll
-        for (int q = 0; q < A; ++q) {
-          const float p = expf(lp[q]);
-          dout[q] = dlpa * ((q == act ? 1.0f : 0.0f) - p) + dent * (-p * (lp[q] + ent));
-        }
+        const float ent = log_softmax<A>(out);
+        const PolicyTerms lt = policy_seed<A>(a, row, m, inv_m, out, ent, dout);
+        lsum0 += cnt ? lt.loss : 0.f;
+        lsum1 += cnt ? lt.ent : 0.f;
+        lsum2 += cnt ? lt.ratio : 0.f;
       } else {
-        const float v = out[0];
-        const float old = a.old_value[row];
-        const float tgt = (a.returns[row] - a.stats[MM_MST_VN_MEAN]) / a.stats[MM_MST_VN_STD];
-        const float dv = v - old;
-        const float vc = old + fminf(fmaxf(dv, -a.clip), a.clip);
-        const float eo = tgt - v, ec = tgt - vc;
-        const float hd = a.huber_delta;
-        const float lo = fabsf(eo) <= hd ? eo * eo * 0.5f : hd * (fabsf(eo) - hd * 0.5f);
-        const float lc = fabsf(ec) <= hd ? ec * ec * 0.5f : hd * (fabsf(ec) - hd * 0.5f);
-        const float go = -(fabsf(eo) <= hd ? eo : (eo > 0.f ? hd : -hd));
-        const float gc =
-            -(fabsf(ec) <= hd ? ec : (ec > 0.f ? hd : -hd)) * ((dv >= -a.clip && dv <= a.clip) ? 1.0f : 0.0f);
-        const float d = lo > lc ? go : (lc > lo ? gc : 0.5f * (go + gc));
-        dout[0] = a.value_coef * m * inv_m * d;
-        lsum0 += (h == 0 && valid) ? fmaxf(lo, lc) * m : 0.f;
+        const float lt = value_seed(a, row, m, inv_m, out[0], dout[0]);
+        lsum0 += cnt ? lt : 0.f;
       }
       if (!valid) {   // a tail lane: an exact zero whatever the clamped row holds
 #pragma unroll
@@ -2011,157 +2096,16 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
       }
       wave_fence();
     }
-    // ---- from here pass M (mlp_body): LN2 backward (x2 = LN2(a2), a2 = relu(W2 f1 + b2)); f1 = LN1(a1)
-    float da[16], xh[16], tt[16], f1[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xh[q] = (mp.a2[q] - mp.mu2) * mp.rs2;
-    ln32_bwd(dxv, xh, mp.rs2, lv + LO::ln2w, da);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      tt[q] = dxv[q] * xh[q];
-      da[q] = mp.a2[q] > 0.f ? da[q] : 0.f;
-      xh[q] = (mp.a1[q] - mp.mu1) * mp.rs1;
-      f1[q] = xh[q] * lv[LO::ln1w + kperm(q, h)] + lv[LO::ln1b + kperm(q, h)];
-    }
-    tput(S0, da);
-    tput(S1, f1);
-    tput(S2, tt);
-    const float s_a2 = scale_for(wave_max(absmax16(da)));
-    // ---- LN1 backward: dx1 = W2^T da2 (one scale per column), then da1
-    float dx1[16], da1[16];
-    {
-      const float c_a = scale_for(col_max(absmax16(da)));
-      S16 sa;
-      split16s(da, c_a, sa);
-      f32x16 acc;
-      zero16(acc);
-      mmh(smb + GM::W2T, sa, acc);
-      const float u = 1.0f / (sw * c_a);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) dx1[q] = acc[q] * u;
-      ln32_bwd(dx1, xh, mp.rs1, lv + LO::ln1w, da1);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        tt[q] = dx1[q] * xh[q];
-        da1[q] = mp.a1[q] > 0.f ? da1[q] : 0.f;
-      }
-    }
-    wave_fence();
-    // dW2 += da2 f1^T, db2
-    float At[16];
-    {
-      float Bt[16];
-      tget(S0, At);
-      tget(S1, Bt);
-      sl2w += tsum(S2);
-      wave_fence();
-      tput(S0, da1);
-      tput(S1, dxv);
-      tput(S2, tt);
-      S16 sa, sb;
-      split16s(At, s_a2, sa);
-      split16s(Bt, s_f1, sb);
-      f32x16 tmp;
-      zero16(tmp);
-      accg(tmp, sa, sb);
-      acc_unscale(aW2, tmp, 1.0f / (s_a2 * s_f1));
-#pragma unroll
-      for (int s = 0; s < 16; ++s) sb2 += At[s];
-    }
-    const float s_a1 = scale_for(wave_max(absmax16(da1)));
-    wave_fence();
-    sl2b += tsum(S1);
-    sl1w += tsum(S2);
-    tget(S0, At);   // da1 transposed
-    wave_fence();
-    tput(S1, dx1);
-    wave_fence();
-    sl1b += tsum(S1);
-    wave_fence();
-    // ---- L1 / LN0: dW1 += da1 f0^T, db1, df0 = W1^T da1 -> LN0 parameter gradients
-    {
-      S16 sa;
-      split16s(At, s_a1, sa);
-#pragma unroll
-      for (int s = 0; s < 16; ++s) sb1 += At[s];
-      const float c_b = scale_for(col_max(absmax16(da1)));
-      S16 sd;
-      split16s(da1, c_b, sd);
-      const float u_b = 1.0f / (sw * c_b), u_w = 1.0f / (s_a1 * s_f0);
-      float x[WIDE ? 1 : DT][16];
-      if constexpr (!WIDE) load_obs<D, DT>(orow, x);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        float x0[16], f0[16], dfv[16];
-        if constexpr (WIDE) load_obs_tile<D>(orow, t, x[0]);   // (streamed again: the wide row is not kept)
-        const float (&xt)[16] = x[WIDE ? 0 : t];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int f = 32 * t + kperm(q, h);
-          x0[q] = (xt[q] - mp.mu0) * mp.rs0;
-          f0[q] = x0[q] * lv[LO::ln0w + f] + lv[LO::ln0b + f];
-        }
-        tput(S0, f0);
-        f32x16 acc;
-        zero16(acc);
-        mmh(smb + GM::W1T + t * HBLK, sd, acc);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          dfv[q] = acc[q] * u_b;
-          tt[q] = dfv[q] * x0[q];
-        }
-        tput(S1, tt);
-        tput(S2, dfv);
-        wave_fence();
-        float Bt[16];
-        tget(S0, Bt);
-        sl0w[t] += tsum(S1);
-        sl0b[t] += tsum(S2);
-        S16 sb;
-        split16s(Bt, s_f0, sb);
-        f32x16 tmp;
-        zero16(tmp);
-        accg(tmp, sa, sb);
-        acc_unscale(aW1[t], tmp, u_w);
-        wave_fence();
-      }
-    }
+    mb.tile(smb, lv, sw, s_f0, s_f1, mp, orow, dxv, S0, S1, S2, h);
   }
 
-  // ---- loss sums (logging only, train_info): one atomic per wave
-  if (a.loss_acc) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lsum0 += __shfl_xor(lsum0, o);
-      lsum1 += __shfl_xor(lsum1, o);
-      lsum2 += __shfl_xor(lsum2, o);
-    }
-    if (lane == 0) {
-      if constexpr (O == A) {
-        atomicAdd(&a.loss_acc[MM_MLOSS_POLICY], lsum0 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_ENTROPY], lsum1 * inv_m);
-        atomicAdd(&a.loss_acc[MM_MLOSS_RATIO], lsum2);
-      } else {
-        atomicAdd(&a.loss_acc[MM_MLOSS_VALUE], lsum0 * inv_m);
-      }
-    }
-  }
+  loss_flush<O == A>(a.loss_acc, lsum0, lsum1, lsum2, inv_m);
 
   // ---- block reduction (fixed order) into the flat gradient layout (the recurrent tensors stay zero), one partial
   __syncthreads();
   float* red = sm;
   for (int e = threadIdx.x; e < F::total; e += blockDim.x) red[e] = 0.f;
-  sb2 = xsum(sb2);
-  sb1 = xsum(sb1);
-  sl2w = xsum(sl2w);
-  sl2b = xsum(sl2b);
-  sl1w = xsum(sl1w);
-  sl1b = xsum(sl1b);
-#pragma unroll
-  for (int t = 0; t < DT; ++t) {
-    sl0w[t] = xsum(sl0w[t]);
-    sl0b[t] = xsum(sl0b[t]);
-  }
+  mb.fold();
 #pragma unroll
   for (int o = 0; o < O; ++o) {
     aWo[o] = xsum(aWo[o]);
@@ -2171,27 +2115,8 @@ __device__ void ffg_body(const FfGradArgs& k, int net, float* sm) {
   __syncthreads();
   for (int ww = 0; ww < MWV; ++ww) {
     if (w == ww) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int mm = kperm(q, h);
-        red[F::W2 + mm * H + ci] += aW2[q];
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-          if (32 * t + ci < D) red[F::W1 + mm * F::Dp + 32 * t + ci] += aW1[t][q];
-      }
+      mb.add(red, ci, h);
       if (h == 0) {
-        red[F::b2 + ci] += sb2;
-        red[F::b1 + ci] += sb1;
-        red[F::ln2_w + ci] += sl2w;
-        red[F::ln2_b + ci] += sl2b;
-        red[F::ln1_w + ci] += sl1w;
-        red[F::ln1_b + ci] += sl1b;
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-          if (32 * t + ci < D) {
-            red[F::ln0_w + 32 * t + ci] += sl0w[t];
-            red[F::ln0_b + 32 * t + ci] += sl0b[t];
-          }
 #pragma unroll
         for (int o = 0; o < O; ++o) {
           red[F::Wo + o * H + ci] += aWo[o];
