@@ -1147,12 +1147,123 @@ __device__ __forceinline__ void load_obs_ks(const float* orow, int kb, int D, fl
   }
 }
 
+// Compile-time step policy of agent_q_fwd_body_h3 / q_epilogue16.
+// StepGeneric: everything is decided at run time from p.io (Q mode, draw source, q_out, training saves, h_out store):
+// every caller but the chunk kernel's fp16x3 step loop.
+// StepChunk: what that loop always runs: device draws through rng_in only, no q_out, no io.save, the Q head limited to
+// tile 0 (the hand-off words carry 4-bit actions: rows 0-15), h1's split handed on as the next step's h0 split, and
+// the epilogue of the block's role (MM_Q_MAX target, MM_Q_ACT behavior) behind ONE scalar branch on the wave-uniform
+// io.mode (q_epilogue16_chunk<MODE>). The forward itself is instantiated once for both roles, and h_out is still
+// written from inside it (by store_h, the launch's last step): a forward per role, a peeled last step or a write-back
+// after the loop each raised the kernel's spill count and put scratch traffic into the step loop.
+struct StepGeneric {
+  static constexpr bool kGeneric = true;
+};
+struct StepChunk {
+  static constexpr bool kGeneric = false;
+};
+
+// x(lane) and x(lane ^ 16) / x(lane ^ 32) without an LDS round trip (v_permlane16_swap / v_permlane32_swap of a value
+// with itself): lo is the value of the pair's lower lane (even 16-lane row / lanes 0-31), hi that of the upper one,
+// the same two values in both lanes of a pair. Every lane of the wave must be active.
+struct LanePair {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ LanePair lane_pair16(uint32_t v) {
+  const auto x = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  return LanePair{x[0], x[1]};
+}
+__device__ __forceinline__ LanePair lane_pair32(uint32_t v) {
+  const auto x = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return LanePair{x[0], x[1]};
+}
+
+// The chunk step's epilogue (StepChunk policy): q_epilogue16's values, with
+// - the argmax / gather exchanges as lane-pair swaps (the pair's two candidates are combined in one fixed order, so both
+//   lanes hold the same winner: the tie rule (lower row) does not depend on which lane owns which candidate);
+// - the eps-greedy draws of TWO steps per pass: at even launch steps lanes g in {0, 1} draw for this step and lanes g in
+//   {2, 3} for the next one (even g the uniform, odd g the random action: the (seed, counter + step, rng_in) streams of
+//   the per-step draws), reduced to one decision per lane (-1 greedy, else the random action) that `carry` hands to
+//   the odd step, which draws nothing. Parity is relative to the launch's first step; no state crosses launches.
+template <int MODE>
+__device__ __forceinline__ int q_epilogue16_chunk(const QFwdParams& p, int agent, int e, bool valid, const f32x4& q0,
+                                                  float eps, uint64_t ctr, int64_t out_off, const uint64_t* rng_in,
+                                                  bool odd_step, int& carry) {
+  const int g = (threadIdx.x & 63) >> 4;
+  const mm_qfwd_io& io = p.io;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 4 * g + r;
+    const float v = q0[r];
+    if (row < p.A && (v > best || (v == best && row < bi))) {
+      best = v;
+      bi = row;
+    }
+  }
+  auto better = [&](const LanePair& v, const LanePair& ix) {
+    const float fa = __uint_as_float(v.lo), fb = __uint_as_float(v.hi);
+    const int ia = (int)ix.lo, ib = (int)ix.hi;
+    const bool tb = fb > fa || (fb == fa && ib < ia);
+    best = tb ? fb : fa;
+    bi = tb ? ib : ia;
+  };
+  better(lane_pair16(__float_as_uint(best)), lane_pair16((uint32_t)bi));
+  better(lane_pair32(__float_as_uint(best)), lane_pair32((uint32_t)bi));
+  static_assert(MODE == MM_Q_ACT || MODE == MM_Q_MAX, "chunk step epilogue: behavior (ACT) or target (MAX)");
+  if constexpr (MODE == MM_Q_MAX) {
+    if (valid && g == 0) io.qsel_out[out_off + (int64_t)e * p.N + agent] = best;
+    return bi;
+  } else {
+    int dec;
+    if (!odd_step) {
+      const bool ra_lane = (g & 1) != 0;
+      const uint64_t sd = ra_lane ? io.seed ^ 0x5bd1e995ull : io.seed;
+      const uint64_t r = rng_draw_premul(sd, (g & 2) ? rng_counter_mul(ctr + 1) : rng_counter_mul(ctr), *rng_in);
+      const float uu = rng_uniform(r);
+      const uint32_t Au = (uint32_t)p.A;
+      const uint32_t ra = rng_mod_small_u(r, Au, 0xFFFFFFFFu / Au, (0xFFFFFFFFu % Au + 1u) % Au);
+      const float u = __uint_as_float(lane_pair16(__float_as_uint(uu)).lo);   // the even-g lane's uniform
+      const int d = u <= eps ? (int)lane_pair16(ra).hi : -1;                   // the odd-g lane's random action
+      const LanePair dd = lane_pair32((uint32_t)d);
+      dec = (int)dd.lo;
+      carry = (int)dd.hi;
+    } else {
+      dec = carry;
+    }
+    const int act = dec >= 0 ? dec : bi;
+    float mine = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * g + r == act) mine = q0[r];
+    const LanePair m16 = lane_pair16(__float_as_uint(mine));
+    mine = __uint_as_float(m16.lo) + __uint_as_float(m16.hi);
+    const LanePair m32 = lane_pair32(__float_as_uint(mine));
+    mine = __uint_as_float(m32.lo) + __uint_as_float(m32.hi);
+    if (valid && g == 0) {
+      const int64_t o = out_off + (int64_t)e * p.N + agent;
+      io.act_out[o] = act;
+      io.qsel_out[o] = mine;
+    }
+    return act;
+  }
+}
+
 // Q output / argmax / eps-greedy / gather epilogue for 16-row Q tiles (rows 16t + 4g + r).
 // out_off: element offset of the act / qsel outputs (the fused rollout step's ring slot)
-template <int AT>
+// POL: the step policy; a StepChunk policy runs q_epilogue16_chunk on tile 0 (odd_step / carry: its two-step draws)
+template <int AT, class POL = StepGeneric>
 __device__ __forceinline__ int q_epilogue16(const QFwdParams& p, int agent, int e, bool valid,
                                             const f32x4 (&qa)[AT], float eps, uint64_t ctr, int64_t out_off = 0,
-                                            const uint64_t* rng_in = nullptr) {
+                                            const uint64_t* rng_in = nullptr, bool odd_step = false,
+                                            int* carry = nullptr) {
+  if constexpr (!POL::kGeneric) {
+    // (the role by the wave-uniform io.mode: a scalar branch around the two epilogues)
+    if (p.io.mode == MM_Q_ACT)
+      return q_epilogue16_chunk<MM_Q_ACT>(p, agent, e, valid, qa[0], eps, ctr, out_off, rng_in, odd_step, *carry);
+    return q_epilogue16_chunk<MM_Q_MAX>(p, agent, e, valid, qa[0], eps, ctr, out_off, rng_in, odd_step, *carry);
+  }
   const int g = (threadIdx.x & 63) >> 4;
   const mm_qfwd_io& io = p.io;
   if (valid && io.q_out) {
@@ -1240,15 +1351,18 @@ __device__ __forceinline__ int q_epilogue16(const QFwdParams& p, int agent, int 
 }
 
 // ol(kb, x) loads observation k-step kb (lane (c, g) holds features 32 kb + kperm16(j, g) of env e)
-template <int F1, int G, int H, int AB, class OL>
+// POL: the step policy (StepGeneric / StepChunk above; odd_step / carry: the chunk epilogue's two-step draws)
+template <int F1, int G, int H, int AB, class OL, class POL = StepGeneric>
 __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agent, int e,
                                                     const float* __restrict__ W, const OL& ol,
                                                     float (&xn)[8], const f32x4 (&h0)[H / 16], float eps,
                                                     uint64_t ctr, int64_t out_off = 0, int x16_from_kb = 1 << 30,
                                                     f32x4 (*h1_keep)[H / 16] = nullptr, bool store_h = true,
-                                                    const uint64_t* rng_in = nullptr) {
+                                                    const uint64_t* rng_in = nullptr, bool odd_step = false,
+                                                    int* carry = nullptr, KS (*hs_carry)[H / 32] = nullptr) {
   using CG = QnetCGeo<F1, G, H, AB>;
   constexpr int T1 = F1 / 16, T2 = G / 16, TH = H / 16, AT = (AB * 32 + 15) / 16;
+  constexpr int QT = POL::kGeneric ? AT : 1;   // Q tiles computed
   constexpr int RB1 = F1 / 32, RB2 = G / 32, HB = H / 32;
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4;
@@ -1312,7 +1426,9 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
     for (int r = 0; r < 4; ++r) x1[t][r] = relu_bits(x1[t][r]);
 #pragma unroll
   for (int kb = 0; kb < RB1; ++kb) split_pair(x1[2 * kb], x1[2 * kb + 1], x1s[kb]);
-  float* sv = (io.save && valid) ? io.save + ((int64_t)e * p.N + agent) * (F1 + G + 6 * H) : nullptr;
+  float* sv = nullptr;
+  if constexpr (POL::kGeneric)
+    sv = (io.save && valid) ? io.save + ((int64_t)e * p.N + agent) * (F1 + G + 6 * H) : nullptr;
   if (sv) {
 #pragma unroll
     for (int t = 0; t < T1; ++t)
@@ -1340,11 +1456,17 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
 
   // ---- GRU cell (h0 loaded by the caller at kernel start)
   KS h0s[HB];
+  if constexpr (!POL::kGeneric) {   // (the caller's split of h0: the previous step's h1 split, zero where h0 was reset)
 #pragma unroll
-  for (int kb = 0; kb < HB; ++kb) split_pair(h0[2 * kb], h0[2 * kb + 1], h0s[kb]);
-  float* hop = (valid && io.h_out && store_h) ? io.h_out + (int64_t)e * io.hout_se + (int64_t)agent * io.hout_sa +
-                                         (int64_t)(4 * g) * io.hout_sf
-                                   : nullptr;
+    for (int kb = 0; kb < HB; ++kb) h0s[kb] = (*hs_carry)[kb];
+  } else {
+#pragma unroll
+    for (int kb = 0; kb < HB; ++kb) split_pair(h0[2 * kb], h0[2 * kb + 1], h0s[kb]);
+  }
+  // (the chunk launch requires h_out: no null test in its policy)
+  float* hop = (valid && (!POL::kGeneric || io.h_out) && store_h)
+                   ? io.h_out + (int64_t)e * io.hout_se + (int64_t)agent * io.hout_sa + (int64_t)(4 * g) * io.hout_sf
+                   : nullptr;
   // GRU: per hidden tile t and k-step, the three gates' fragments are read together and their
   // 9 MFMAs interleaved (gate r, z, n, r, z, n, ...): consecutive MFMAs are independent, so no
   // accumulator read-after-write stall between them.
@@ -1435,18 +1557,22 @@ __device__ __forceinline__ int agent_q_fwd_body_h3(const QFwdParams& p, int agen
   KS h1s[HB];
 #pragma unroll
   for (int kb = 0; kb < HB; ++kb) split_pair(h1[2 * kb], h1[2 * kb + 1], h1s[kb]);
+  if constexpr (!POL::kGeneric) {
+#pragma unroll
+    for (int kb = 0; kb < HB; ++kb) (*hs_carry)[kb] = h1s[kb];
+  }
 
   // ---- Q head (only the 16-row tiles that hold real actions)
-  f32x4 qa[AT];
+  f32x4 qa[QT];
 #pragma unroll
-  for (int t = 0; t < AT; ++t) {
+  for (int t = 0; t < QT; ++t) {
     qa[t] = wbias(CG::off_bq, t);
-    if (t < ATr) {
+    if (!POL::kGeneric || t < ATr) {
 #pragma unroll
       for (int kb = 0; kb < HB; ++kb) mmb(CG::off_q + ((t >> 1) * HB + kb) * 1024, t & 1, h1s[kb], qa[t]);
     }
   }
-  return q_epilogue16<AT>(p, agent, e, valid, qa, eps, ctr, out_off, rng_in);
+  return q_epilogue16<QT, POL>(p, agent, e, valid, qa, eps, ctr, out_off, rng_in, odd_step, carry);
 }
 
 // ---- prologue pieces shared by the 1024-thread kernels (one agent's image in LDS per block)
@@ -2071,6 +2197,8 @@ __device__ __forceinline__ void roll_chunk_steps() {
   for (int t = 0; t < H / 16; ++t) hkeep[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   // behavior lanes: the (env, agent) part of the eps-greedy draws (rng_inner) is the same every step
   uint64_t rin = 0;
+  KS hsk[H / 32] = {};
+  int dcarry = -1;   // behavior lanes: the odd steps' eps-greedy decision, drawn at the even step before
   if (!EXACT) {
     const ChunkCtx c0x = chunk_ctx<F1, G, H, AB>(kargs0);
     const int l0 = (int)threadIdx.x & 63;
@@ -2361,6 +2489,14 @@ __device__ __forceinline__ void roll_chunk_steps() {
 #pragma unroll
         for (int t = 0; t < H / 16; ++t) h0[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
+      // the split of h0 the forward reads: that of the previous step's h1 (handed on by the body), zero on a reset
+      if (i == 0) {
+#pragma unroll
+        for (int kb = 0; kb < H / 32; ++kb) split_pair(h0[2 * kb], h0[2 * kb + 1], hsk[kb]);
+      } else if (e >= E || rt || bd) {
+#pragma unroll
+        for (int kb = 0; kb < H / 32; ++kb) hsk[kb] = KS{};
+      }
       float* dst = (!second && srow >= 0) ? rc.store_obs + srow * rc.row_stride + nxt_off + (int64_t)agent * D : nullptr;
       const int ls = e < E ? le : 0;
       const int rcw = cx.spq[ls * N + agent] & 0xFF;
@@ -2393,15 +2529,19 @@ __device__ __forceinline__ void roll_chunk_steps() {
       }
       // (the image base offset by the per-step opaque zero: the fragment addresses are formed inside the step,
       // not hoisted out of the loop into registers that then spill)
-      const int a = agent_q_fwd_body_h3<F1, G, H, AB>(p, agent, e, wsm_ptr() + tz, ol, xn, h0, cx.eps, ctr, off, 1,
-                                                      &hkeep, i + 1 == nsteps, &rin);
+      // (StepChunk policy: what this loop always runs; odd launch steps take their eps-greedy decision from dcarry)
+      const int a = agent_q_fwd_body_h3<F1, G, H, AB, decltype(ol), StepChunk>(
+          p, agent, e, wsm_ptr() + tz, ol, xn, h0, cx.eps, ctr, off, 1, &hkeep, i + 1 == nsteps, &rin, (i & 1) != 0,
+          &dcarry, &hsk);
       // behavior blocks: each wave publishes its 16 envs' actions of step t + 1 as soon as its forward is done (every
       // lane (c, g) holds env c's action): lanes 0-7 / 8-15 OR their nibbles into the two hand-off words of the wave
       if (second && i + 1 < rc.n) {
         uint32_t v = ((uint32_t)a & 15u) << (4 * (lane & 7));
-        v |= __shfl_xor(v, 1);
-        v |= __shfl_xor(v, 2);
-        v |= __shfl_xor(v, 4);
+        // (OR over each 8 lanes by DPP: quad_perm [1, 0, 3, 2], quad_perm [2, 3, 0, 1], then row_half_mirror, which
+        // pairs the two quads of a half row once every quad is uniform; every lane of the wave is active here)
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
         if (lane == 0 || lane == 8) {
           uint64_t* hd = rc.hx + (((int64_t)tile * rc.hxl + i + 1) * N + agent) * 32 + wave * 2 + (lane >> 3);
           __hip_atomic_store(hd, ((uint64_t)((uint32_t)cx.seq + 1u) << 32) | v, __ATOMIC_RELAXED,
@@ -3301,6 +3441,9 @@ int rollout_chunk(mm_env* env, const mm_qnet_dims* d, const float* packed_t, con
   MM_REQUIRE(io_b->eps_ptr && io_b->act_out && io_b->qsel_out && io_t->qsel_out,
              "rollout_chunk: behavior eps_ptr / act_out / qsel_out and target qsel_out required");
   MM_REQUIRE(io_b->reset == nullptr && io_t->reset == nullptr, "rollout_chunk: reset flags come from the env (pass NULL)");
+  MM_REQUIRE(d->n_actions <= 16, "rollout_chunk: the hand-off words carry 4-bit actions (n_actions <= 16)");
+  MM_REQUIRE(!io_b->u && !io_b->rand_act && !io_b->save && !io_t->save && !io_b->q_out && !io_t->q_out,
+             "rollout_chunk: device draws only, no q_out / save (the step loop's compile-time policy)");
   const int64_t nd = (int64_t)d->n_agents * d->obs_dim;
   MM_REQUIRE(x->row_stride >= (x->chunk_len + 1) * nd, "rollout_chunk: row stride too small");
   QFwdParams p0, p1;

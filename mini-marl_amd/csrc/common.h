@@ -54,6 +54,13 @@ __device__ __forceinline__ uint64_t rng_inner(uint64_t a, uint64_t b) { return m
 __device__ __forceinline__ uint64_t rng_draw_inner(uint64_t seed, uint64_t counter, uint64_t inner) {
   return mix64(seed ^ mix64(counter * 0xD1B54A32D192ED03ull ^ inner));
 }
+// rng_draw_inner split once more at its counter part: rng_draw_inner(seed, counter, inner) ==
+// rng_draw_premul(seed, rng_counter_mul(counter), inner), so lanes that draw for different (wave-uniform) counters
+// select between scalar products instead of multiplying per lane
+__device__ __forceinline__ uint64_t rng_counter_mul(uint64_t counter) { return counter * 0xD1B54A32D192ED03ull; }
+__device__ __forceinline__ uint64_t rng_draw_premul(uint64_t seed, uint64_t cmul, uint64_t inner) {
+  return mix64(seed ^ mix64(cmul ^ inner));
+}
 // x % m for a wave-uniform 1 <= m <= 65536 without a division: q0 = umulhi(x, floor((2^32 - 1) / m)) is floor(x / m)
 // or up to 2 below it, so x - q0 m lies in [0, 3 m) and two conditional subtractions make it exact
 __device__ __forceinline__ uint32_t umod_small(uint32_t x, uint32_t m, uint32_t minv) {
