@@ -158,6 +158,12 @@ int mm_clip_adam_pack(float* P, float* G, float* m, float* v, int64_t n, int64_t
   if (rc) return rc;
   MM_REQUIRE(o.total <= n, "clip_adam_pack: the agent net (%lld params) must lead P (%lld)", (long long)o.total,
              (long long)n);
+  // every refusal comes before the first launch: sumsq_kernel already advances the Adam step
+  if (next_per) {
+    MM_REQUIRE(!per && next_nodes && next_slots && next_isw && batch >= 1 && batch <= mm::PS_T * mm::PER_SAMPLE_MAXJ,
+               "clip_adam_pack: the next sample needs its outputs and no priority update in the same launch");
+    MM_REQUIRE(next_per->n_data > 0, "per_sample: empty buffer");
+  }
   const int nb = 256;
   hipLaunchKernelGGL(mm::sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)s, G, n_clip, partials, step);
   MM_HIP_CHECK(hipGetLastError());
@@ -175,9 +181,6 @@ int mm_clip_adam_pack(float* P, float* G, float* m, float* v, int64_t n, int64_t
   mm::PerSmp ps = {};
   const bool per_block = per && nodes && td && (per->cap & (per->cap - 1)) == 0 && batch >= 1 && batch <= mm::PU_B;
   if (next_per) {   // sample the next update's batch (this update's priorities must be in already)
-    MM_REQUIRE(!per && next_nodes && next_slots && next_isw && batch >= 1 && batch <= mm::PS_T * mm::PER_SAMPLE_MAXJ,
-               "clip_adam_pack: the next sample needs its outputs and no priority update in the same launch");
-    MM_REQUIRE(next_per->n_data > 0, "per_sample: empty buffer");
     const double decay = per_sample_prep(next_per);
     ps = {next_per->tree, next_per->cap, next_per->st, next_seed, next_counter, decay, next_nodes, next_slots,
           next_isw, batch};

@@ -37,6 +37,28 @@ def rng_uniform(r):
     return ((_u64(r) >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
 
 
+PER_TAG_STRATIFIED, PER_TAG_UNIFORM = 77, 91
+
+
+def _unit53(seed, ctr, B, tag):
+    """(rng_draw(seed, ctr, k, tag) >> 11) * 2**-53 for k < B: a float64 in [0, 1), exact."""
+    r = rng_draw(np.uint64(seed), np.uint64(ctr), np.arange(B, dtype=np.uint64), np.uint64(tag))
+    return (r >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def per_stratum_fracs(seed, ctr, B):
+    """The chunk PER's stratum fractions when none are injected (per_small.h per_sample_body, tag 77);
+    ``ctr`` is the call's counter argument plus the device's sample-call count."""
+    return _unit53(seed, ctr, B, PER_TAG_STRATIFIED)
+
+
+def per_uniform_slots(seed, ctr, B, n):
+    """The uniform chunk sampler's slots over n filled slots (per.hip per_uniform_kernel, tag 91):
+    min(n - 1, int(u * n))."""
+    u = _unit53(seed, ctr, B, PER_TAG_UNIFORM)
+    return np.minimum(np.int64(n - 1), (u * np.float64(n)).astype(np.int64))
+
+
 def eps_greedy_draws(seed, counter, n_envs, n_agents, n_actions):
     """The fused forward's epsilon-greedy draws for one step (agent_fwd.hip, MM_Q_ACT epilogue):
     one uniform per env row (all agents of a row explore together, vdn/_network.py:53) and a
