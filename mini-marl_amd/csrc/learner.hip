@@ -19,6 +19,7 @@
 #include "common.h"
 #include "minimarl.h"
 #include "per_small.h"
+#include "qmix_cell.h"
 
 namespace mm {
 // large-batch kernel shape (mm_learner_set_multi_sample): B >= 512 runs the mixer forward / recurrence backward with
@@ -150,9 +151,7 @@ __host__ __device__ inline MixOff mix_offsets(int S, int Hm, int K1, int N) {
   return o;
 }
 
-// per-(t,b) mixer save row: [hm0 | r | z | n | anh | hm1 | w1raw (N*K1) | b1 | w2raw | b2pre | ypre | b2]
-__host__ __device__ inline int mix_save_dim(int Hm, int K1, int N) { return 6 * Hm + N * K1 + 4 * K1 + 1; }
-
+// (the per-(t, b) mixer save row and delta row: MixSaveRow / MixDeltaRow, qmix_cell.h)
 struct MixFwdNet {
   const float* P;        // mixer params (canonical)
   const float* gi;       // [B][3Hm] precomputed W_ih s + b_ih of this step (mixer_gi_kernel) or nullptr
@@ -423,22 +422,12 @@ __device__ __forceinline__ void mixer_fwd_body(const MixFwdArgs& a, const MixFwd
   }
   block_matvec(nt.P + o.gWhh, nt.P + o.gbhh, 3 * Hm, Hm, h0, gh);
   __syncthreads();
-  float* sv = nt.save ? nt.save + (int64_t)b * mix_save_dim(Hm, K1, N) : nullptr;
+  float* svp = nt.save ? nt.save + (int64_t)b * mix_save_dim(Hm, K1, N) : nullptr;
   for (int i = threadIdx.x; i < Hm; i += blockDim.x) {
-    const float r = sigmoidf_(gi[i] + gh[i]);
-    const float z = sigmoidf_(gi[Hm + i] + gh[Hm + i]);
-    const float n = tanhf_(gi[2 * Hm + i] + r * gh[2 * Hm + i]);
-    const float hv = n + z * (h0[i] - n);
-    h1[i] = hv;
-    nt.h_out[(int64_t)b * Hm + i] = hv;
-    if (sv) {
-      sv[i] = h0[i];
-      sv[Hm + i] = r;
-      sv[2 * Hm + i] = z;
-      sv[3 * Hm + i] = n;
-      sv[4 * Hm + i] = gh[2 * Hm + i];
-      sv[5 * Hm + i] = hv;
-    }
+    const GruFwd c = gru_cell_fwd(gi[i], gi[Hm + i], gi[2 * Hm + i], gh[i], gh[Hm + i], gh[2 * Hm + i], h0[i]);
+    h1[i] = c.h1;
+    nt.h_out[(int64_t)b * Hm + i] = c.h1;
+    if (svp) store_gru_save(MixSaveRow<float*>(svp, Hm, K1, N), i, h0[i], gh[2 * Hm + i], c);
   }
   __syncthreads();
   // hypernets on h1: w1raw [N*K1], b1 [K1], w2raw [K1], b2 hidden pre-ReLU [K1]
@@ -447,30 +436,17 @@ __device__ __forceinline__ void mixer_fwd_body(const MixFwdArgs& a, const MixFwd
   block_matvec(nt.P + o.w2W, nt.P + o.w2b, K1, Hm, h1, hyp + N * K1 + K1);
   block_matvec(nt.P + o.b2aW, nt.P + o.b2ab, K1, Hm, h1, hyp + N * K1 + 2 * K1);
   __syncthreads();
-  // y_pre[k] = sum_i |w1raw[k*N + i]| q_i + b1[k]   (bmm(W1 [K1,N], q [N,1]) + b1)
-  for (int k = threadIdx.x; k < K1; k += blockDim.x) {
-    float acc = 0.f;
-    for (int i = 0; i < N; ++i) acc += fabsf(hyp[k * N + i]) * nt.q[(int64_t)b * N + i];
-    yp[k] = acc + hyp[N * K1 + k];
-  }
+  for (int k = threadIdx.x; k < K1; k += blockDim.x) yp[k] = mix_ypre(k, K1, N, hyp, nt.q + (int64_t)b * N);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float* w2raw = hyp + N * K1 + K1;
-    const float* b2pre = hyp + N * K1 + 2 * K1;
-    float b2 = 0.f;
-    for (int k = 0; k < K1; ++k) b2 += nt.P[o.b2bW + k] * fmaxf(b2pre[k], 0.f);
-    b2 += nt.P[o.b2bb];
-    float acc = 0.f;
-    for (int k = 0; k < K1; ++k) acc += fabsf(w2raw[k]) * fmaxf(yp[k], 0.f);
-    nt.qtot[b] = acc + b2;
-    if (sv) sv[6 * Hm + N * K1 + 4 * K1] = b2;
+    const MixOut m = mix_qtot(K1, N, hyp, yp, nt.P + o.b2bW, nt.P + o.b2bb);
+    nt.qtot[b] = m.qtot;
+    if (svp) *MixSaveRow<float*>(svp, Hm, K1, N).b2 = m.b2;
   }
-  if (sv) {
-    // [w1raw | b1 | w2raw | relu(b2 hidden)] (relu'd: the b2 weight gradient needs it, and its
-    // mask relu(x) > 0 equals x > 0)
-    for (int i = threadIdx.x; i < N * K1 + 3 * K1; i += blockDim.x)
-      sv[6 * Hm + i] = i >= N * K1 + 2 * K1 ? fmaxf(hyp[i], 0.f) : hyp[i];
-    for (int k = threadIdx.x; k < K1; k += blockDim.x) sv[6 * Hm + N * K1 + 3 * K1 + k] = yp[k];
+  if (svp) {   // the save row's hypernet part and y_pre (layout: MixSaveRow, qmix_cell.h)
+    const MixSaveRow<float*> sv(svp, Hm, K1, N);
+    for (int i = threadIdx.x; i < N * K1 + 3 * K1; i += blockDim.x) sv.w1raw[i] = mix_save_hyp(i, K1, N, hyp[i]);
+    for (int k = threadIdx.x; k < K1; k += blockDim.x) sv.ypre[k] = yp[k];
   }
 }
 
@@ -512,37 +488,27 @@ __device__ __forceinline__ void mixer_hyper_rows(const MixFwdArgs& a, const MixF
     for (int q = 0; q < MIX_SPB; ++q) hyp[q * RW + r] = acc[q] + bb;
   }
   __syncthreads();
+  const int svd = mix_save_dim(Hm, K1, N);
   for (int idx = threadIdx.x; idx < ns * K1; idx += blockDim.x) {
     const int sI = idx / K1, k = idx % K1, b = b0 + sI;
-    const float* hp = hyp + sI * RW;
-    float acc = 0.f;
-    for (int i = 0; i < N; ++i) acc += fabsf(hp[k * N + i]) * nt.q[(int64_t)b * N + i];
-    yp[sI * K1 + k] = acc + hp[NK + k];
+    yp[sI * K1 + k] = mix_ypre(k, K1, N, hyp + sI * RW, nt.q + (int64_t)b * N);
   }
   __syncthreads();
   if ((int)threadIdx.x < ns) {
     const int sI = threadIdx.x, b = b0 + sI;
-    const float* hp = hyp + sI * RW;
-    const float* w2raw = hp + NK + K1;
-    const float* b2pre = hp + NK + 2 * K1;
-    float b2 = 0.f;
-    for (int k = 0; k < K1; ++k) b2 += nt.P[o.b2bW + k] * fmaxf(b2pre[k], 0.f);
-    b2 += nt.P[o.b2bb];
-    float acc = 0.f;
-    for (int k = 0; k < K1; ++k) acc += fabsf(w2raw[k]) * fmaxf(yp[sI * K1 + k], 0.f);
-    nt.qtot[b] = acc + b2;
-    if (nt.save) nt.save[(int64_t)b * mix_save_dim(Hm, K1, N) + 6 * Hm + NK + 4 * K1] = b2;
+    const MixOut m = mix_qtot(K1, N, hyp + sI * RW, yp + sI * K1, nt.P + o.b2bW, nt.P + o.b2bb);
+    nt.qtot[b] = m.qtot;
+    if (nt.save) *MixSaveRow<float*>(nt.save + (int64_t)b * svd, Hm, K1, N).b2 = m.b2;
   }
   if (nt.save) {
     for (int idx = threadIdx.x; idx < ns * RW; idx += blockDim.x) {
       const int sI = idx / RW, i = idx % RW;
-      float* sv = nt.save + (int64_t)(b0 + sI) * mix_save_dim(Hm, K1, N);
-      const float v = hyp[sI * RW + i];
-      sv[6 * Hm + i] = i >= NK + 2 * K1 ? fmaxf(v, 0.f) : v;
+      const MixSaveRow<float*> sv(nt.save + (int64_t)(b0 + sI) * svd, Hm, K1, N);
+      sv.w1raw[i] = mix_save_hyp(i, K1, N, hyp[sI * RW + i]);
     }
     for (int idx = threadIdx.x; idx < ns * K1; idx += blockDim.x) {
       const int sI = idx / K1, k = idx % K1;
-      nt.save[(int64_t)(b0 + sI) * mix_save_dim(Hm, K1, N) + 6 * Hm + NK + 3 * K1 + k] = yp[sI * K1 + k];
+      MixSaveRow<float*>(nt.save + (int64_t)(b0 + sI) * svd, Hm, K1, N).ypre[k] = yp[sI * K1 + k];
     }
   }
 }
@@ -598,22 +564,13 @@ __global__ __launch_bounds__(256) void mixer_fwd_multi_kernel(MixFwdArgs a) {
     const int sI = idx / Hm, i = idx % Hm, b = b0 + sI;
     const float* gI = gi + sI * 3 * Hm;
     const float* gH = gh + sI * 3 * Hm;
-    const float r = sigmoidf_(gI[i] + gH[i]);
-    const float z = sigmoidf_(gI[Hm + i] + gH[Hm + i]);
-    const float n = tanhf_(gI[2 * Hm + i] + r * gH[2 * Hm + i]);
     const float h0v = h0[sI * Hm + i];
-    const float hv = n + z * (h0v - n);
-    h1[sI * Hm + i] = hv;
-    nt.h_out[(int64_t)b * Hm + i] = hv;
-    if (nt.save) {
-      float* sv = nt.save + (int64_t)b * mix_save_dim(Hm, K1, N);
-      sv[i] = h0v;
-      sv[Hm + i] = r;
-      sv[2 * Hm + i] = z;
-      sv[3 * Hm + i] = n;
-      sv[4 * Hm + i] = gH[2 * Hm + i];
-      sv[5 * Hm + i] = hv;
-    }
+    const GruFwd c = gru_cell_fwd(gI[i], gI[Hm + i], gI[2 * Hm + i], gH[i], gH[Hm + i], gH[2 * Hm + i], h0v);
+    h1[sI * Hm + i] = c.h1;
+    nt.h_out[(int64_t)b * Hm + i] = c.h1;
+    if (nt.save)
+      store_gru_save(MixSaveRow<float*>(nt.save + (int64_t)b * mix_save_dim(Hm, K1, N), Hm, K1, N), i, h0v,
+                     gH[2 * Hm + i], c);
   }
   __syncthreads();
   mixer_hyper_rows(a, nt, b0, ns, h1, hyp, yp);
@@ -824,11 +781,9 @@ struct MixBwdArgs {
   const float* done;     // [B] done of THIS step (1 => drop the future gradient)
   float* dhm;            // [B][Hm] in: grad wrt hm1 from step t+1 ; out: grad wrt hm0 (for step t-1)
   float* dqa;            // [B][N] out
-  float* delta;          // [B][MDD] out: [dgi 3Hm | dgh 3Hm | dw1raw N*K1 | db1 K1 | dw2raw K1 | db2pre K1 | dQ 1]
+  float* delta;          // [B][MDD] out: one MixDeltaRow (qmix_cell.h) per sample
   int B, N, S, Hm, K1;
 };
-__host__ __device__ inline int mix_delta_dim(int Hm, int K1, int N) { return 6 * Hm + N * K1 + 3 * K1 + 1; }
-
 __device__ __forceinline__ void mixer_bwd_body(const MixBwdArgs& a, int b);
 
 __global__ __launch_bounds__(256) void mixer_bwd_kernel(MixBwdArgs a) { mixer_bwd_body(a, blockIdx.x); }
@@ -859,54 +814,20 @@ __device__ __forceinline__ void mixer_bwd_body(const MixBwdArgs& a, int b) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int Hm = a.Hm, K1 = a.K1, N = a.N;
   const MixOff o = mix_offsets(a.S, Hm, K1, N);
-  const float* sv = a.save + (int64_t)b * mix_save_dim(Hm, K1, N);
-  const float* hm0 = sv;
-  const float* rg = sv + Hm;
-  const float* zg = sv + 2 * Hm;
-  const float* ng = sv + 3 * Hm;
-  const float* anh = sv + 4 * Hm;
-  const float* w1raw = sv + 6 * Hm;
-  const float* w2raw = w1raw + N * K1 + K1;
-  const float* b2pre = w2raw + K1;
-  const float* ypre = b2pre + K1;
-  float* dl = a.delta + (int64_t)b * mix_delta_dim(Hm, K1, N);
-  float* d_w1 = dl + 6 * Hm;         // [N*K1]
-  float* d_b1 = d_w1 + N * K1;       // [K1]
-  float* d_w2 = d_b1 + K1;           // [K1]
-  float* d_b2pre = d_w2 + K1;        // [K1]
+  const MixSaveRow<const float*> sv(a.save + (int64_t)b * mix_save_dim(Hm, K1, N), Hm, K1, N);
+  const MixDeltaRow<float*> dl(a.delta + (int64_t)b * mix_delta_dim(Hm, K1, N), Hm, K1, N);
   float* dhm1 = sm;                  // [Hm]
   float* dgh = dhm1 + Hm;            // [3Hm]
   float* shd = dgh + 3 * Hm;         // [N*K1 + 3*K1] local copy of the hypernet deltas
   float* red = shd + N * K1 + 3 * K1;  // [4*Hm] wave partials of the transposed mat-vecs
   const float dQ = a.dq[b];
   // hypernet / mixing deltas
-  for (int k = threadIdx.x; k < K1; k += blockDim.x) {
-    const float y = fmaxf(ypre[k], 0.f);
-    const float w2 = w2raw[k];
-    const float dw2 = dQ * y * (w2 > 0.f ? 1.f : (w2 < 0.f ? -1.f : 0.f));
-    const float dyp = ypre[k] > 0.f ? dQ * fabsf(w2) : 0.f;
-    const float db2p = b2pre[k] > 0.f ? dQ * a.P[o.b2bW + k] : 0.f;
-    d_b1[k] = dyp;
-    d_w2[k] = dw2;
-    d_b2pre[k] = db2p;
-    shd[N * K1 + k] = dyp;
-    shd[N * K1 + K1 + k] = dw2;
-    shd[N * K1 + 2 * K1 + k] = db2p;
-    for (int i = 0; i < N; ++i) {
-      const float w = w1raw[k * N + i];
-      const float dw1 = dyp * a.qa[(int64_t)b * N + i] * (w > 0.f ? 1.f : (w < 0.f ? -1.f : 0.f));
-      d_w1[k * N + i] = dw1;
-      shd[k * N + i] = dw1;
-    }
-  }
-  if (threadIdx.x == 0) dl[6 * Hm + N * K1 + 3 * K1] = dQ;
+  for (int k = threadIdx.x; k < K1; k += blockDim.x)
+    mix_hyper_delta(k, K1, N, sv, a.qa + (int64_t)b * N, dQ, a.P + o.b2bW, dl, shd);
+  if (threadIdx.x == 0) *dl.dQ = dQ;
   __syncthreads();
-  // dqa_i = sum_k dy_pre_k |W1[k,i]|
-  for (int i = threadIdx.x; i < N; i += blockDim.x) {
-    float acc = 0.f;
-    for (int k = 0; k < K1; ++k) acc += shd[N * K1 + k] * fabsf(w1raw[k * N + i]);
-    a.dqa[(int64_t)b * N + i] = acc;
-  }
+  for (int i = threadIdx.x; i < N; i += blockDim.x)
+    a.dqa[(int64_t)b * N + i] = mix_dqa(i, K1, N, shd + N * K1, sv.w1raw);
   // dhm1 = (future grad unless done) + hypernet input grads
   const bool drop = a.done[b] > 0.5f;
   for (int c = threadIdx.x; c < Hm; c += blockDim.x) dhm1[c] = drop ? 0.f : a.dhm[(int64_t)b * Hm + c];
@@ -917,27 +838,15 @@ __device__ __forceinline__ void mixer_bwd_body(const MixBwdArgs& a, int b) {
   block_matvec_t(a.P + o.b2aW, K1, Hm, shd + N * K1 + 2 * K1, dhm1, true, red);
   // GRU backward (h' = n + z (h - n))
   for (int i = threadIdx.x; i < Hm; i += blockDim.x) {
-    const float dh = dhm1[i];
-    const float r = rg[i], z = zg[i], n = ng[i];
-    const float dn = dh * (1.f - z);
-    const float dz = dh * (hm0[i] - n);
-    const float dpn = dn * (1.f - n * n);
-    const float dr = dpn * anh[i];
-    const float dar = dr * r * (1.f - r);
-    const float daz = dz * z * (1.f - z);
-    dl[i] = dar;
-    dl[Hm + i] = daz;
-    dl[2 * Hm + i] = dpn;
-    dl[3 * Hm + i] = dar;
-    dl[4 * Hm + i] = daz;
-    dl[5 * Hm + i] = dpn * r;
-    dgh[i] = dar;
-    dgh[Hm + i] = daz;
-    dgh[2 * Hm + i] = dpn * r;
+    const GruBwd c = gru_cell_bwd(dhm1[i], sv.hm0[i], sv.r[i], sv.z[i], sv.n[i], sv.anh[i]);
+    store_gru_delta(dl.dgi, dl.dgh, i, Hm, c);
+    dgh[i] = c.dar;
+    dgh[Hm + i] = c.daz;
+    dgh[2 * Hm + i] = c.dpn_r;
   }
   __syncthreads();
   // dhm0 = z * dhm1 + W_hh^T dgh
-  for (int c = threadIdx.x; c < Hm; c += blockDim.x) shd[c] = dhm1[c] * zg[c];
+  for (int c = threadIdx.x; c < Hm; c += blockDim.x) shd[c] = dhm1[c] * sv.z[c];
   __syncthreads();
   block_matvec_t(a.P + o.gWhh, 3 * Hm, Hm, dgh, shd, true, red);
   for (int c = threadIdx.x; c < Hm; c += blockDim.x) a.dhm[(int64_t)b * Hm + c] = shd[c];
@@ -1013,42 +922,19 @@ __global__ __launch_bounds__(256) void mixer_bwd_seq_multi_kernel(MixBwdArgs a0,
     // hypernet / mixing deltas
     for (int idx = threadIdx.x; idx < ns * K1; idx += blockDim.x) {
       const int s = idx / K1, k = idx % K1, b = b0 + s;
-      const float* w1raw = save + (int64_t)b * svd + 6 * Hm;
-      const float* w2raw = w1raw + NK + K1;
-      const float* b2pre = w2raw + K1;
-      const float* ypre = b2pre + K1;
-      float* dl = delta + (int64_t)b * dld;
-      float* sh = shd + s * SH;
-      const float dQ = dqv[b];
-      const float y = fmaxf(ypre[k], 0.f);
-      const float w2 = w2raw[k];
-      const float dw2 = dQ * y * (w2 > 0.f ? 1.f : (w2 < 0.f ? -1.f : 0.f));
-      const float dyp = ypre[k] > 0.f ? dQ * fabsf(w2) : 0.f;
-      const float db2p = b2pre[k] > 0.f ? dQ * a0.P[o.b2bW + k] : 0.f;
-      dl[6 * Hm + NK + k] = dyp;
-      dl[6 * Hm + NK + K1 + k] = dw2;
-      dl[6 * Hm + NK + 2 * K1 + k] = db2p;
-      sh[NK + k] = dyp;
-      sh[NK + K1 + k] = dw2;
-      sh[NK + 2 * K1 + k] = db2p;
-      for (int i = 0; i < N; ++i) {
-        const float wv = w1raw[k * N + i];
-        const float dw1 = dyp * qa[(int64_t)b * N + i] * (wv > 0.f ? 1.f : (wv < 0.f ? -1.f : 0.f));
-        dl[6 * Hm + k * N + i] = dw1;
-        sh[k * N + i] = dw1;
-      }
+      mix_hyper_delta(k, K1, N, MixSaveRow<const float*>(save + (int64_t)b * svd, Hm, K1, N), qa + (int64_t)b * N,
+                      dqv[b], a0.P + o.b2bW, MixDeltaRow<float*>(delta + (int64_t)b * dld, Hm, K1, N),
+                      shd + s * SH);
     }
     if ((int)threadIdx.x < ns) {
       const int b = b0 + threadIdx.x;
-      delta[(int64_t)b * dld + 6 * Hm + NK + 3 * K1] = dqv[b];
+      *MixDeltaRow<float*>(delta + (int64_t)b * dld, Hm, K1, N).dQ = dqv[b];
     }
     __syncthreads();
     for (int idx = threadIdx.x; idx < ns * N; idx += blockDim.x) {
       const int s = idx / N, i = idx % N, b = b0 + s;
-      const float* w1raw = save + (int64_t)b * svd + 6 * Hm;
-      float acc = 0.f;
-      for (int k = 0; k < K1; ++k) acc += shd[s * SH + NK + k] * fabsf(w1raw[k * N + i]);
-      dqa[(int64_t)b * N + i] = acc;
+      dqa[(int64_t)b * N + i] =
+          mix_dqa(i, K1, N, shd + s * SH + NK, MixSaveRow<const float*>(save + (int64_t)b * svd, Hm, K1, N).w1raw);
     }
     for (int idx = threadIdx.x; idx < Q * Hm; idx += blockDim.x) {
       const int s = idx / Hm, c = idx % Hm, b = b0 + s;
@@ -1066,26 +952,14 @@ __global__ __launch_bounds__(256) void mixer_bwd_seq_multi_kernel(MixBwdArgs a0,
         dgh[s * 3 * Hm + i] = dgh[s * 3 * Hm + Hm + i] = dgh[s * 3 * Hm + 2 * Hm + i] = 0.f;
         continue;
       }
-      const float* sv = save + (int64_t)b * svd;
-      const float dh = dhm1[idx];
-      const float r = sv[Hm + i], z = sv[2 * Hm + i], n = sv[3 * Hm + i];
-      const float dn = dh * (1.f - z);
-      const float dz = dh * (sv[i] - n);
-      const float dpn = dn * (1.f - n * n);
-      const float dr = dpn * sv[4 * Hm + i];
-      const float dar = dr * r * (1.f - r);
-      const float daz = dz * z * (1.f - z);
-      float* dl = delta + (int64_t)b * dld;
-      dl[i] = dar;
-      dl[Hm + i] = daz;
-      dl[2 * Hm + i] = dpn;
-      dl[3 * Hm + i] = dar;
-      dl[4 * Hm + i] = daz;
-      dl[5 * Hm + i] = dpn * r;
-      dgh[s * 3 * Hm + i] = dar;
-      dgh[s * 3 * Hm + Hm + i] = daz;
-      dgh[s * 3 * Hm + 2 * Hm + i] = dpn * r;
-      shd[s * SH + i] = dh * z;   // dhm0 direct path (hypernet deltas are consumed)
+      const MixSaveRow<const float*> sv(save + (int64_t)b * svd, Hm, K1, N);
+      const MixDeltaRow<float*> dl(delta + (int64_t)b * dld, Hm, K1, N);
+      const GruBwd c = gru_cell_bwd(dhm1[idx], sv.hm0[i], sv.r[i], sv.z[i], sv.n[i], sv.anh[i]);
+      store_gru_delta(dl.dgi, dl.dgh, i, Hm, c);
+      dgh[s * 3 * Hm + i] = c.dar;
+      dgh[s * 3 * Hm + Hm + i] = c.daz;
+      dgh[s * 3 * Hm + 2 * Hm + i] = c.dpn_r;
+      shd[s * SH + i] = c.dh_z;   // dhm0 direct path (hypernet deltas are consumed)
     }
     __syncthreads();
     block_matvec_t_multi(a0.P + o.gWhh, 3 * Hm, Hm, dgh, 3 * Hm, shd, SH, red);
@@ -1161,51 +1035,16 @@ __global__ __launch_bounds__(256) void mixer_bwd_seq_lds_kernel(MixBwdArgs a, Mi
       const int i = ti + j * 256;
       nx[j] = (t > 0 && i < SI) ? step_ptr(t - 1, i) : 0.f;
     }
-    const float* sv = inb + (t & 1) * SI;
-    const float* qa = sv + svd;
+    const MixSaveRow<const float*> sv(inb + (t & 1) * SI, Hm, K1, N);   // (the staged copy, in LDS)
+    const float* qa = sv.end;
     const float dQ = qa[N];
     const float done_b = qa[N + 1];
     float* dqa = a.dqa + t * sq.dqa_st;
-    float* dl = a.delta + t * sq.delta_st + (int64_t)b * dld;
-    const float* hm0 = sv;
-    const float* rg = sv + Hm;
-    const float* zg = sv + 2 * Hm;
-    const float* ng = sv + 3 * Hm;
-    const float* anh = sv + 4 * Hm;
-    const float* w1raw = sv + 6 * Hm;
-    const float* w2raw = w1raw + NK + K1;
-    const float* b2pre = w2raw + K1;
-    const float* ypre = b2pre + K1;
-    float* d_w1 = dl + 6 * Hm;
-    float* d_b1 = d_w1 + NK;
-    float* d_w2 = d_b1 + K1;
-    float* d_b2pre = d_w2 + K1;
-    for (int k = ti; k < K1; k += blockDim.x) {
-      const float y = fmaxf(ypre[k], 0.f);
-      const float w2 = w2raw[k];
-      const float dw2 = dQ * y * (w2 > 0.f ? 1.f : (w2 < 0.f ? -1.f : 0.f));
-      const float dyp = ypre[k] > 0.f ? dQ * fabsf(w2) : 0.f;
-      const float db2p = b2pre[k] > 0.f ? dQ * b2w[k] : 0.f;
-      d_b1[k] = dyp;
-      d_w2[k] = dw2;
-      d_b2pre[k] = db2p;
-      shd[NK + k] = dyp;
-      shd[NK + K1 + k] = dw2;
-      shd[NK + 2 * K1 + k] = db2p;
-      for (int i = 0; i < N; ++i) {
-        const float w = w1raw[k * N + i];
-        const float dw1 = dyp * qa[i] * (w > 0.f ? 1.f : (w < 0.f ? -1.f : 0.f));
-        d_w1[k * N + i] = dw1;
-        shd[k * N + i] = dw1;
-      }
-    }
-    if (ti == 0) dl[6 * Hm + NK + 3 * K1] = dQ;
+    const MixDeltaRow<float*> dl(a.delta + t * sq.delta_st + (int64_t)b * dld, Hm, K1, N);
+    for (int k = ti; k < K1; k += blockDim.x) mix_hyper_delta(k, K1, N, sv, qa, dQ, b2w, dl, shd);
+    if (ti == 0) *dl.dQ = dQ;
     lds_sync();
-    for (int i = ti; i < N; i += blockDim.x) {
-      float acc = 0.f;
-      for (int k = 0; k < K1; ++k) acc += shd[NK + k] * fabsf(w1raw[k * N + i]);
-      dqa[(int64_t)b * N + i] = acc;
-    }
+    for (int i = ti; i < N; i += blockDim.x) dqa[(int64_t)b * N + i] = mix_dqa(i, K1, N, shd + NK, sv.w1raw);
     const bool drop = done_b > 0.5f;
     for (int c = ti; c < Hm; c += blockDim.x) dhm1[c] = drop ? 0.f : dhm[c];
     lds_sync();
@@ -1214,26 +1053,14 @@ __global__ __launch_bounds__(256) void mixer_bwd_seq_lds_kernel(MixBwdArgs a, Mi
     block_matvec_t_ld(img + (M3 + NK + K1) * ld, ld, K1, Hm, shd + NK + K1, dhm1, red);
     block_matvec_t_ld(img + (M3 + NK + 2 * K1) * ld, ld, K1, Hm, shd + NK + 2 * K1, dhm1, red);
     for (int i = ti; i < Hm; i += blockDim.x) {
-      const float dh = dhm1[i];
-      const float r = rg[i], z = zg[i], n = ng[i];
-      const float dn = dh * (1.f - z);
-      const float dz = dh * (hm0[i] - n);
-      const float dpn = dn * (1.f - n * n);
-      const float dr = dpn * anh[i];
-      const float dar = dr * r * (1.f - r);
-      const float daz = dz * z * (1.f - z);
-      dl[i] = dar;
-      dl[Hm + i] = daz;
-      dl[2 * Hm + i] = dpn;
-      dl[3 * Hm + i] = dar;
-      dl[4 * Hm + i] = daz;
-      dl[5 * Hm + i] = dpn * r;
-      dgh[i] = dar;
-      dgh[Hm + i] = daz;
-      dgh[2 * Hm + i] = dpn * r;
+      const GruBwd c = gru_cell_bwd(dhm1[i], sv.hm0[i], sv.r[i], sv.z[i], sv.n[i], sv.anh[i]);
+      store_gru_delta(dl.dgi, dl.dgh, i, Hm, c);
+      dgh[i] = c.dar;
+      dgh[Hm + i] = c.daz;
+      dgh[2 * Hm + i] = c.dpn_r;
     }
     lds_sync();
-    for (int c = ti; c < Hm; c += blockDim.x) shd[c] = dhm1[c] * zg[c];
+    for (int c = ti; c < Hm; c += blockDim.x) shd[c] = dhm1[c] * sv.z[c];
     lds_sync();
     block_matvec_t_ld(img, ld, M3, Hm, dgh, shd, red);
     for (int c = ti; c < Hm; c += blockDim.x) dhm[c] = shd[c];
@@ -1449,21 +1276,11 @@ __device__ __forceinline__ void mixer_rec_fwd_body(const MixFwdArgs& a, const Mi
       const bool zero_next = rs[tt + 1] != 0.f;
       float* sv = nt.save ? nt.save + t * sq.save_st + (int64_t)b * svd : nullptr;
       for (int i = ti; i < HM; i += blockDim.x) {
-        const float r = sigmoidf_(gI[i] + gh[i]);
-        const float z = sigmoidf_(gI[HM + i] + gh[HM + i]);
-        const float n = tanhf_(gI[2 * HM + i] + r * gh[2 * HM + i]);
         const float h0v = h0[i];
-        const float hv = n + z * (h0v - n);
-        h1[i] = zero_next ? 0.f : hv;
-        nt.h_out[t * sq.hout_st + (int64_t)b * HM + i] = hv;
-        if (sv) {
-          sv[i] = h0v;
-          sv[HM + i] = r;
-          sv[2 * HM + i] = z;
-          sv[3 * HM + i] = n;
-          sv[4 * HM + i] = gh[2 * HM + i];
-          sv[5 * HM + i] = hv;
-        }
+        const GruFwd c = gru_cell_fwd(gI[i], gI[HM + i], gI[2 * HM + i], gh[i], gh[HM + i], gh[2 * HM + i], h0v);
+        h1[i] = zero_next ? 0.f : c.h1;
+        nt.h_out[t * sq.hout_st + (int64_t)b * HM + i] = c.h1;
+        if (sv) store_gru_save(MixSaveRow<float*>(sv, HM, a.K1, a.N), i, h0v, gh[2 * HM + i], c);
       }
       if (ts) ts[3] = clock64();
       lds_sync();
@@ -1546,44 +1363,21 @@ __global__ __launch_bounds__(256) void mixer_hyper_bwd_kernel(MixBwdArgs a, int 
   if (tr) tr[1] = clock64();
   for (int idx = threadIdx.x; idx < ns * K1; idx += blockDim.x) {
     const int s = idx / K1, k = idx % K1, b = b0 + s;
-    const float* w1raw = a.save + (int64_t)b * svd + 6 * Hm;
-    const float* w2raw = w1raw + NK + K1;
-    const float* b2pre = w2raw + K1;
-    const float* ypre = b2pre + K1;
-    float* dl = a.delta + (int64_t)b * dld;
-    float* sh = shd + s * SH;
-    const float dQ = a.dq[b];
-    const float y = fmaxf(ypre[k], 0.f);
-    const float w2 = w2raw[k];
-    const float dw2 = dQ * y * (w2 > 0.f ? 1.f : (w2 < 0.f ? -1.f : 0.f));
-    const float dyp = ypre[k] > 0.f ? dQ * fabsf(w2) : 0.f;
-    const float db2p = b2pre[k] > 0.f ? dQ * a.P[o.b2bW + k] : 0.f;
-    dl[6 * Hm + NK + k] = dyp;
-    dl[6 * Hm + NK + K1 + k] = dw2;
-    dl[6 * Hm + NK + 2 * K1 + k] = db2p;
-    sh[NK + k] = dyp;
-    sh[NK + K1 + k] = dw2;
-    sh[NK + 2 * K1 + k] = db2p;
-    for (int i = 0; i < N; ++i) {
-      const float wv = w1raw[k * N + i];
-      const float dw1 = dyp * a.qa[(int64_t)b * N + i] * (wv > 0.f ? 1.f : (wv < 0.f ? -1.f : 0.f));
-      dl[6 * Hm + k * N + i] = dw1;
-      sh[k * N + i] = dw1;
-    }
+    mix_hyper_delta(k, K1, N, MixSaveRow<const float*>(a.save + (int64_t)b * svd, Hm, K1, N), a.qa + (int64_t)b * N,
+                    a.dq[b], a.P + o.b2bW, MixDeltaRow<float*>(a.delta + (int64_t)b * dld, Hm, K1, N),
+                    shd + s * SH);
   }
   if ((int)threadIdx.x < ns) {
     const int b = b0 + threadIdx.x;
-    a.delta[(int64_t)b * dld + 6 * Hm + NK + 3 * K1] = a.dq[b];
+    *MixDeltaRow<float*>(a.delta + (int64_t)b * dld, Hm, K1, N).dQ = a.dq[b];
   }
   if (tr) tr[2] = clock64();
   __syncthreads();
   if (tr) tr[3] = clock64();
   for (int idx = threadIdx.x; idx < ns * N; idx += blockDim.x) {
     const int s = idx / N, i = idx % N, b = b0 + s;
-    const float* w1raw = a.save + (int64_t)b * svd + 6 * Hm;
-    float acc = 0.f;
-    for (int k = 0; k < K1; ++k) acc += shd[s * SH + NK + k] * fabsf(w1raw[k * N + i]);
-    a.dqa[(int64_t)b * N + i] = acc;
+    a.dqa[(int64_t)b * N + i] =
+        mix_dqa(i, K1, N, shd + s * SH + NK, MixSaveRow<const float*>(a.save + (int64_t)b * svd, Hm, K1, N).w1raw);
   }
   if (tr) tr[4] = clock64();
   block_matvec_t_multi<false>(wim, NK, Hm, shd, SH, xo, 4 * Hm, red);
@@ -1652,24 +1446,14 @@ __device__ __forceinline__ void mixer_rec_bwd_body(const MixBwdArgs& a, const Mi
         float dh = dnw[tt] > 0.5f ? 0.f : dhm_c;
 #pragma unroll
         for (int j = 0; j < 4; ++j) dh = dh + in[(5 + j) * HM + i];
-        const float r = in[HM + i], z = in[2 * HM + i], n = in[3 * HM + i];
-        const float dn = dh * (1.f - z);
-        const float dz = dh * (in[i] - n);
-        const float dpn = dn * (1.f - n * n);
-        const float dr = dpn * in[4 * HM + i];
-        const float dar = dr * r * (1.f - r);
-        const float daz = dz * z * (1.f - z);
-        float* dl = a.delta + t * sq.delta_st + (int64_t)b * dld;
-        dl[i] = dar;
-        dl[HM + i] = daz;
-        dl[2 * HM + i] = dpn;
-        dl[3 * HM + i] = dar;
-        dl[4 * HM + i] = daz;
-        dl[5 * HM + i] = dpn * r;
-        dgh[i] = dar;
-        dgh[HM + i] = daz;
-        dgh[2 * HM + i] = dpn * r;
-        shd_c = dh * z;
+        const MixSaveRow<const float*> sv(in, HM, a.K1, a.N);   // (its first 5 HM words, staged in LDS)
+        const MixDeltaRow<float*> dl(a.delta + t * sq.delta_st + (int64_t)b * dld, HM, a.K1, a.N);
+        const GruBwd c = gru_cell_bwd(dh, sv.hm0[i], sv.r[i], sv.z[i], sv.n[i], sv.anh[i]);
+        store_gru_delta(dl.dgi, dl.dgh, i, HM, c);
+        dgh[i] = c.dar;
+        dgh[HM + i] = c.daz;
+        dgh[2 * HM + i] = c.dpn_r;
+        shd_c = c.dh_z;
       }
       if (ts) ts[1] = clock64();
       lds_sync();
@@ -1834,25 +1618,13 @@ __device__ __forceinline__ void agent_bwd_body(const AgentBwdArgs& a) {
     for (int c = lane; c < A; c += 64) a.dq[(int64_t)pair * A + c] = (c == act) ? dqa : 0.f;
   for (int f = lane; f < H && on; f += 64) {
     const float dh1 = Wq[(int64_t)act * H + f] * dqa + (drop ? 0.f : a.dh[(int64_t)pair * H + f]);
-    const float r = h0[H + f], z = h0[2 * H + f], n = h0[3 * H + f], anh = h0[4 * H + f];
-    const float dn = dh1 * (1.f - z);
-    const float dz = dh1 * (h0[f] - n);
-    const float dpn = dn * (1.f - n * n);
-    const float dar = dpn * anh * r * (1.f - r);
-    const float daz = dz * z * (1.f - z);
-    float* gi = a.dgi + (int64_t)pair * 3 * H;
-    float* gh = a.dgh + (int64_t)pair * 3 * H;
-    gi[f] = dar;
-    gi[H + f] = daz;
-    gi[2 * H + f] = dpn;
-    gh[f] = dar;
-    gh[H + f] = daz;
-    gh[2 * H + f] = dpn * r;
-    sdg[w][f] = dar;
-    sdg[w][H + f] = daz;
-    sdg[w][2 * H + f] = dpn * r;
+    const GruBwd c = gru_cell_bwd(dh1, h0[f], h0[H + f], h0[2 * H + f], h0[3 * H + f], h0[4 * H + f]);
+    store_gru_delta(a.dgi + (int64_t)pair * 3 * H, a.dgh + (int64_t)pair * 3 * H, f, H, c);
+    sdg[w][f] = c.dar;
+    sdg[w][H + f] = c.daz;
+    sdg[w][2 * H + f] = c.dpn_r;
     // stash dh1*z for the direct path
-    a.dh[(int64_t)pair * H + f] = dh1 * z;
+    a.dh[(int64_t)pair * H + f] = c.dh_z;
   }
   __syncthreads();
   for (int f = lane; f < H && on; f += 64) {
@@ -1968,24 +1740,12 @@ __device__ __forceinline__ void agent_bwd_seq_body(const AgentBwdArgs& a, const 
         if (f < H) {
           const bool drop = sc[2] > 0.5f;
           const float dh1 = wq[act * H + f] * dqa + (drop ? 0.f : dh);
-          const float r = in[H + f], z = in[2 * H + f], n = in[3 * H + f], anh = in[4 * H + f];
-          const float dn = dh1 * (1.f - z);
-          const float dz = dh1 * (in[f] - n);
-          const float dpn = dn * (1.f - n * n);
-          const float dar = dpn * anh * r * (1.f - r);
-          const float daz = dz * z * (1.f - z);
-          float* gi = a.dgi + t * sq.dgi_st + pair * H3;
-          float* gh = a.dgh + t * sq.dgi_st + pair * H3;
-          gi[f] = dar;
-          gi[H + f] = daz;
-          gi[2 * H + f] = dpn;
-          gh[f] = dar;
-          gh[H + f] = daz;
-          gh[2 * H + f] = dpn * r;
-          sdw[f] = dar;
-          sdw[H + f] = daz;
-          sdw[2 * H + f] = dpn * r;
-          stash = dh1 * z;
+          const GruBwd c = gru_cell_bwd(dh1, in[f], in[H + f], in[2 * H + f], in[3 * H + f], in[4 * H + f]);
+          store_gru_delta(a.dgi + t * sq.dgi_st + pair * H3, a.dgh + t * sq.dgi_st + pair * H3, f, H, c);
+          sdw[f] = c.dar;
+          sdw[H + f] = c.daz;
+          sdw[2 * H + f] = c.dpn_r;
+          stash = c.dh_z;
         }
       }
       if (ts) ts[1] = clock64();
@@ -2064,24 +1824,12 @@ __global__ __launch_bounds__(256) void agent_bwd_multi_kernel(AgentBwdArgs a) {
     if (f < H) {
       const bool drop = a.done[b] > 0.5f;
       const float dh1 = Wq[(int64_t)act * H + f] * dqa + (drop ? 0.f : a.dh[pair * H + f]);
-      const float r = h0[H + f], z = h0[2 * H + f], n = h0[3 * H + f], anh = h0[4 * H + f];
-      const float dn = dh1 * (1.f - z);
-      const float dz = dh1 * (h0[f] - n);
-      const float dpn = dn * (1.f - n * n);
-      const float dar = dpn * anh * r * (1.f - r);
-      const float daz = dz * z * (1.f - z);
-      float* gi = a.dgi + pair * 3 * H;
-      float* gh = a.dgh + pair * 3 * H;
-      gi[f] = dar;
-      gi[H + f] = daz;
-      gi[2 * H + f] = dpn;
-      gh[f] = dar;
-      gh[H + f] = daz;
-      gh[2 * H + f] = dpn * r;
-      sd[f * BWD_SPW + s] = dar;
-      sd[(H + f) * BWD_SPW + s] = daz;
-      sd[(2 * H + f) * BWD_SPW + s] = dpn * r;
-      acc[s] = dh1 * z;
+      const GruBwd c = gru_cell_bwd(dh1, h0[f], h0[H + f], h0[2 * H + f], h0[3 * H + f], h0[4 * H + f]);
+      store_gru_delta(a.dgi + pair * 3 * H, a.dgh + pair * 3 * H, f, H, c);
+      sd[f * BWD_SPW + s] = c.dar;
+      sd[(H + f) * BWD_SPW + s] = c.daz;
+      sd[(2 * H + f) * BWD_SPW + s] = c.dpn_r;
+      acc[s] = c.dh_z;
     }
   }
   // each wave reads only its own rows of sdg: LDS is in order within a wave
@@ -3143,8 +2891,10 @@ static int mixer_wgrad_jobs(int32_t R, int32_t N, int32_t S, int32_t Hm, int32_t
                             const int64_t* s_off, const float* reset_obs, const float* save, const float* delta,
                             float* dP, mm_outer_args* j) {
   const mm::MixOff o = mm::mix_offsets(S, Hm, K1, N);
+  const mm::MixSaveRow<const float*> sv(save, Hm, K1, N);     // row 0; the rows follow at MSD / MDD
+  const mm::MixDeltaRow<const float*> dl(delta, Hm, K1, N);
   const int64_t MSD = mm::mix_save_dim(Hm, K1, N), MDD = mm::mix_delta_dim(Hm, K1, N);
-  const float* hm1 = save + 5 * Hm;
+  const float* hm1 = sv.h1;
   auto job = [&](int i, const float* U, const float* V, int64_t v_m, const int64_t* voff, int64_t w, int64_t b,
                  int32_t rows, int32_t cols) {
     mm_outer_args& a = j[i];
@@ -3166,13 +2916,13 @@ static int mixer_wgrad_jobs(int32_t R, int32_t N, int32_t S, int32_t Hm, int32_t
     a.accumulate = 0;
     a.groups = 1;
   };
-  job(0, delta, state, s_off ? 0 : S, s_off, o.gWih, o.gbih, 3 * Hm, S);
-  job(1, delta + 3 * Hm, save, MSD, nullptr, o.gWhh, o.gbhh, 3 * Hm, Hm);
-  job(2, delta + 6 * Hm, hm1, MSD, nullptr, o.w1W, o.w1b, N * K1, Hm);
-  job(3, delta + 6 * Hm + N * K1, hm1, MSD, nullptr, o.b1W, o.b1b, K1, Hm);
-  job(4, delta + 6 * Hm + N * K1 + K1, hm1, MSD, nullptr, o.w2W, o.w2b, K1, Hm);
-  job(5, delta + 6 * Hm + N * K1 + 2 * K1, hm1, MSD, nullptr, o.b2aW, o.b2ab, K1, Hm);
-  job(6, delta + 6 * Hm + N * K1 + 3 * K1, save + 6 * Hm + N * K1 + 2 * K1, MSD, nullptr, o.b2bW, o.b2bb, 1, K1);
+  job(0, dl.dgi, state, s_off ? 0 : S, s_off, o.gWih, o.gbih, 3 * Hm, S);
+  job(1, dl.dgh, sv.hm0, MSD, nullptr, o.gWhh, o.gbhh, 3 * Hm, Hm);
+  job(2, dl.d_w1, hm1, MSD, nullptr, o.w1W, o.w1b, N * K1, Hm);
+  job(3, dl.d_b1, hm1, MSD, nullptr, o.b1W, o.b1b, K1, Hm);
+  job(4, dl.d_w2, hm1, MSD, nullptr, o.w2W, o.w2b, K1, Hm);
+  job(5, dl.d_b2pre, hm1, MSD, nullptr, o.b2aW, o.b2ab, K1, Hm);
+  job(6, dl.dQ, sv.b2pre, MSD, nullptr, o.b2bW, o.b2bb, 1, K1);
   return 7;
 }
 

@@ -468,15 +468,19 @@ def test_vdn_double_matches_reference_update(golden):
     pytest.param("qmix", 64, 64, 64, 64, None, id="qmix-64-64-64-64"),
     pytest.param("vdn", 64, 32, 32, 32, None, id="vdn-64-32-32-32"),
     pytest.param("qmix_min", 128, 32, 32, 64, None, id="qmix_min-128-32-32-64"),
-    ("qmix", 64, 64, 64, 64, "w13"), ("qmix", 64, 64, 64, 64, "t50_pair")])
+    ("qmix", 64, 64, 64, 64, "w13"), ("qmix", 64, 64, 64, 64, "t50_pair"),
+    ("qmix", 64, 32, 32, 32, "m_k6"), ("qmix", 64, 32, 32, 16, "m_h16"), ("qmix", 64, 32, 32, 128, "m_h128")])
 def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm, case):
     """REC / mixer fwd / mixer bwd / agent bwd as one launch each for all C steps: bit-identical to
     the per-step launches. case: the batch and shape of that case of tests/learner_cases.py instead (w13: the agent
     BPTT runs two LDS windows, 7 + 6 steps, with dones on both sides of the boundary; t50_pair: B = 50, C = 7, tail
-    blocks in every sequence launch), which pins a window or tail fault to the sequence kernel that has it."""
+    blocks in every sequence launch), which pins a window or tail fault to the sequence kernel that has it. The m_*
+    cases are off the split mixer path, where the mixer's sequence launches are the fallback kernels: m_k6 (K1 = 6)
+    forward recurrence + hypernet launches, backward the LDS-image kernel; m_h16 (Hm 16, K1 8) forward per step,
+    backward the LDS-image kernel; m_h128 (Hm 128) backward the plain loop over the per-step body."""
     from minimarl.learner import Mixer, QLearner
     from minimarl.qnet import AgentQNet
-    N, D, A, B, C = 4, 47, 5, 32, 10
+    N, D, A, B, C, K1 = 4, 47, 5, 32, 10, 32
     gen = torch.Generator().manual_seed(3)
     st, ns = torch.rand(B, C, N, D, generator=gen), torch.rand(B, C, N, D, generator=gen)
     act = torch.randint(0, A, (B, C, N), generator=gen).float()
@@ -486,8 +490,8 @@ def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm, case):
     if case:
         from learner_cases import build_case
         c = build_case(case)
-        assert c.agent == (f1, g, h) and c.mixer == (hm, 32) and c.mode == mode
-        N, D, A, B, C = c.N, c.D, c.A, c.B, c.C
+        assert c.agent == (f1, g, h) and c.mixer[0] == hm and c.mode == mode
+        N, D, A, B, C, K1 = c.N, c.D, c.A, c.B, c.C, c.mixer[1]
         st, act, rew, ns, dn, w = c.batch
     out = []
     for seq in (True, False):
@@ -495,7 +499,7 @@ def test_chunk_sequence_launches_match_per_step(mode, f1, g, h, hm, case):
         tgt = AgentQNet(N, D, A, f1, g, h, DEV, seed=2)
         mix = tmix = None
         if mode != "vdn":
-            mix, tmix = Mixer(N, N * D, hm, 32, DEV, seed=3), Mixer(N, N * D, hm, 32, DEV, seed=4)
+            mix, tmix = Mixer(N, N * D, hm, K1, DEV, seed=3), Mixer(N, N * D, hm, K1, DEV, seed=4)
         L = QLearner(beh, tgt, mix, tmix, batch=B, chunk=C, mode=mode, device=DEV)
         L.seq = seq
         L.load_batch(st, act, rew, ns, dn, w)
