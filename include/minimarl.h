@@ -580,11 +580,12 @@ int mm_clip_adam(float* P, float* G, float* m, float* v, int64_t n, int64_t n_cl
  * layout of mm_mappo_param_offsets (18 tensors: ln0_w ln0_b W1 b1 ln1_w ln1_b W2 b2 ln2_w ln2_b
  * Wih Whh bih bhh lnr_w lnr_b Wo bo + total; W1 rows padded to Dp = ceil4(D), Wo/bo to ceil4(O)).
  * Buffer arrays are [T(+1), EN] row-major with EN = envs*agents (row = t*EN + en); obs rows [.., D],
- * hiddens [.., H]. Supported: H = 32, A = 5, D in {47, 94}.
+ * hiddens [.., H]. Supported: H = 32, A = 5, D in {47, 94, 3} (3: Switch with local observations and the clock).
  * Centralized critic (use_centralized_V; base_runner.py:70-85,155-161, rmappo_policy.py:29-33): with
  * cent_agents = n >= 2 the critic's input is the env's share_obs, the concatenation of its n agents' obs rows
  * (width Dc = n * obs_dim: ln0_w / ln0_b [Dc], W1 [H, Dc] with rows padded to ceil4(Dc)); the actor is
- * unchanged. Supported: obs_dim 47 with cent_agents 2 or 8 (Dc 94 | 376), in mm_mappo_fwd ROLLOUT / VALUES and
+ * unchanged. Supported: obs_dim 47 with cent_agents 2 or 8 (Dc 94 | 376) and obs_dim 3 with cent_agents 2 (Dc 6;
+ * any other cent_agents at obs_dim 3 is refused with a message naming these), in mm_mappo_fwd ROLLOUT / VALUES and
  * mm_mappo_grad; the TRAIN forward, mm_mappo_bwd, mm_mappo_wgrad and mm_mappo_evaluate_actions refuse it. */
 typedef struct mm_mappo_dims {
   int32_t obs_dim, hidden, n_actions;
@@ -665,7 +666,7 @@ int mm_mappo_bwd(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, mm_stream_t
  * through the LN-MLP. Weight gradients are reduced on MFMA inside both. Uses a's P, obs, mask, active, act,
  * adv, old_logp, old_value, returns, stats, loss_acc, coefficients, en, T, L (save / gsoa / rs ignored).
  * Writes the full flat gradient vectors. scratch: mm_mappo_grad_scratch_count(d, L, T, en) floats, 16-byte
- * aligned. H 32, A 5, D 47 | 94. */
+ * aligned. H 32, A 5, D 47 | 94 | 3. */
 int64_t mm_mappo_grad_scratch_count(const mm_mappo_dims* d, int32_t L, int32_t T, int64_t en);
 int mm_mappo_grad(const mm_mappo_dims* d, const mm_mappo_bwd_args* a, const float* h_actor, const float* h_critic,
                   float* grad_actor, float* grad_critic, float* scratch, mm_stream_t s);
@@ -723,7 +724,8 @@ int mm_mappo_insert(const uint8_t* done, int32_t n_agents, int32_t hidden, int64
  * masks are never read. mm_mappo_dims, the argument structs and the flat 18-tensor layout of mm_mappo_param_offsets
  * are the recurrent path's: the six recurrent tensors (Wih Whh bih bhh lnr_w lnr_b) are not read and receive exactly
  * zero gradient (kept at zero, mm_clip_adam leaves them there and the gradient norm is unaffected). Same supported
- * shapes: H 32, A 5, obs_dim 47 | 94, a centralized critic of 2 or 8 agents at obs_dim 47; anything else is an error.
+ * shapes: H 32, A 5, obs_dim 47 | 94 | 3, a centralized critic of 2 or 8 agents at obs_dim 47 and of 2 agents at
+ * obs_dim 3; anything else is an error.
  *
  * mm_mappo_ff_fwd: get_actions / get_values (rmappo_policy.py:57-99) of mm_mappo_fwd's modes MM_MAPPO_ROLLOUT (sample
  * with u or the counter RNG keyed (seed, counter, row), evaluate act_in, or deterministic = first argmax; actor

@@ -758,6 +758,10 @@ static int mappo_eval_launch(const mm_mappo_fwd_args* a, const int32_t* act, con
       using SH = mm::MappoShape<94, 32, 5>;                                           \
       return CALL;                                                                  \
     }                                                                               \
+    if ((d)->hidden == 32 && (d)->n_actions == 5 && (d)->obs_dim == 3) {            \
+      using SH = mm::MappoShape<3, 32, 5>;                                            \
+      return CALL;                                                                  \
+    }                                                                               \
     return mm::mappo_dims_error(d);                                                 \
   } while (0)
 
@@ -770,7 +774,9 @@ static int64_t param_count(const mm_mappo_dims* d, int net) {
   return 2 * Dp + (int64_t)H * Dp + 14 * H + 7 * H * H + (int64_t)Op * H + Op;   // MGeo::total
 }
 static_assert(MGeo<47, 32, 5>::total == 2 * 48 + 32 * 48 + 14 * 32 + 7 * 32 * 32 + 8 * 32 + 8 &&
-                  MGeo<376, 32, 1>::total == 2 * 376 + 32 * 376 + 14 * 32 + 7 * 32 * 32 + 4 * 32 + 4,
+                  MGeo<376, 32, 1>::total == 2 * 376 + 32 * 376 + 14 * 32 + 7 * 32 * 32 + 4 * 32 + 4 &&
+                  MGeo<3, 32, 5>::total == 2 * 4 + 32 * 4 + 14 * 32 + 7 * 32 * 32 + 8 * 32 + 8 &&
+                  MGeo<6, 32, 1>::total == 2 * 8 + 32 * 8 + 14 * 32 + 7 * 32 * 32 + 4 * 32 + 4,
               "param_count restates MGeo::total");
 
 }  // namespace mm
@@ -848,7 +854,8 @@ int mm_mappo_evaluate_actions(const mm_mappo_dims* d, const mm_mappo_fwd_args* a
 int64_t mm_mappo_wgrad_partial_count(const mm_mappo_dims* d, int64_t rs) {
   if (!d || mm::param_count(d, 0) < 0 || mm::mappo_cent_agents(d) > 1) return -1;
   if (d->obs_dim == 47) return mm::MappoShape<47, 32, 5>::partial_count(rs);
-  return mm::MappoShape<94, 32, 5>::partial_count(rs);
+  if (d->obs_dim == 94) return mm::MappoShape<94, 32, 5>::partial_count(rs);
+  return mm::MappoShape<3, 32, 5>::partial_count(rs);
 }
 
 int mm_mappo_wgrad(const mm_mappo_dims* d, int32_t net, const float* gsoa, int64_t rs, float* grad, float* partial,

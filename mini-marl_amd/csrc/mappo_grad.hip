@@ -622,6 +622,12 @@ struct GeoM {
   static constexpr int total = total_for(MW);
 };
 static_assert(GeoH<47, 5>::W2 == GeoM<47, 5>::W2 && GeoH<94, 5>::W2 == GeoM<94, 5>::W2, "W1 / W2 offsets");
+// the 3-wide (Switch) shapes: one 32-feature tile whose features beyond D are staged as zeros, the first layer's
+// products cut to the tile's first k block; the decentralized nets read 12-byte rows by clamped scalar loads
+// (load_obs), the 6-wide critic 24-byte rows in pairs (load_obs_tile: D even, rows 8-byte aligned)
+static_assert(GeoH<3, 5>::W2 == GeoM<3, 5>::W2 && GeoH<6, 1>::W2 == GeoM<6, 1>::W2 && Geo<3, 5>::DT == 1 &&
+                  Geo<6, 1>::DT == 1 && GeoM<3, 5>::MW == 8 && GeoM<6, 1>::MW == 8,
+              "3-wide shapes: one input tile, pass M at 8 waves per block");
 
 // W of split block b at (row i, column k) from the flat MGeo parameters (MI: pass M's image, else pass G's)
 template <int D, int O, bool MI>
@@ -1979,7 +1985,8 @@ struct GeoFM {
   static_assert(total_for(MW) * 4 <= 160 * 1024, "LDS budget of the feed-forward gradient image");
   static_assert(MGeo<D, H, O>::total <= total_for(MW), "the block reduction reuses the image");
 };
-static_assert(GeoFM<47, 5>::MW == 4 && GeoFM<94, 5>::MW == 4 && GeoFM<94, 1>::MW == 4 && GeoFM<376, 1>::MW == 3,
+static_assert(GeoFM<47, 5>::MW == 4 && GeoFM<94, 5>::MW == 4 && GeoFM<94, 1>::MW == 4 && GeoFM<376, 1>::MW == 3 &&
+                  GeoFM<3, 5>::MW == 4 && GeoFM<3, 1>::MW == 4 && GeoFM<6, 1>::MW == 4,
               "waves per block of the feed-forward gradient pass");
 
 struct FfGradArgs {
@@ -2202,6 +2209,8 @@ struct FfGradShape {
     if (D_ == 94 && n_ == 1) return CALL(94, 1);                                       \
     if (D_ == 47 && n_ == 2) return CALL(47, 2);                                       \
     if (D_ == 47 && n_ == 8) return CALL(47, 8);                                       \
+    if (D_ == 3 && n_ == 1) return CALL(3, 1);                                         \
+    if (D_ == 3 && n_ == 2) return CALL(3, 2);                                         \
   } while (0)
 
 // the rollout / get_values forward on MFMA (mappo.hip routes MM_MAPPO_ROLLOUT / VALUES here for the supported dims)

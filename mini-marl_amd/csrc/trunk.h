@@ -21,17 +21,26 @@ struct MGeo {
   static constexpr int total = bo + Op;
 };
 
-// Supported MAPPO shapes (host): H 32, A 5, D 47 | 94 with a decentralized critic (cent_agents 0 | 1), D 47 with a
-// centralized critic over 2 or 8 agents (critic input width 94 | 376).
+// Supported MAPPO shapes (host): H 32, A 5, D 47 | 94 | 3 with a decentralized critic (cent_agents 0 | 1), D 47 with
+// a centralized critic over 2 or 8 agents (critic input width 94 | 376), D 3 (Switch: local obs + clock) with a
+// centralized critic over 2 agents (critic input width 6).
 inline int mappo_cent_agents(const mm_mappo_dims* d) { return d->cent_agents >= 2 ? d->cent_agents : 1; }
 inline bool mappo_dims_supported(const mm_mappo_dims* d) {
   if (d->hidden != 32 || d->n_actions != 5 || d->cent_agents < 0) return false;
-  const int n = mappo_cent_agents(d);
-  return n == 1 ? (d->obs_dim == 47 || d->obs_dim == 94) : (d->obs_dim == 47 && (n == 2 || n == 8));
+  const int n = mappo_cent_agents(d), D = d->obs_dim;
+  if (n == 1) return D == 47 || D == 94 || D == 3;
+  return (D == 47 && (n == 2 || n == 8)) || (D == 3 && n == 2);
 }
 inline int mappo_dims_error(const mm_mappo_dims* d) {
-  set_error("mappo: unsupported dims D=%d H=%d A=%d cent_agents=%d (supported: H 32, A 5, D 47|94; centralized "
-            "critic: D 47 with cent_agents 2|8, critic input width 94|376)",
+  if (d->obs_dim == 3 && d->hidden == 32 && d->n_actions == 5 && d->cent_agents > 2) {
+    set_error("mappo: unsupported dims D=3 cent_agents=%d (critic input width %d): the 3-wide shapes built are "
+              "(obs_dim 3, decentralized critic) and (obs_dim 3, cent_agents 2, critic input width 6)",
+              d->cent_agents, 3 * d->cent_agents);
+    return MM_EINVAL;
+  }
+  set_error("mappo: unsupported dims D=%d H=%d A=%d cent_agents=%d (supported: H 32, A 5, D 47|94|3; centralized "
+            "critic: D 47 with cent_agents 2|8, critic input width 94|376; D 3 with cent_agents 2, critic input "
+            "width 6)",
             d->obs_dim, d->hidden, d->n_actions, d->cent_agents);
   return MM_EINVAL;
 }

@@ -112,15 +112,29 @@ class MappoTrainConfig:
     # centralized critic over the env's share_obs (mappo/_config.py use_centralized_V; MappoPolicy(cent_agents=n_agents))
     use_centralized_V: bool = False
     algorithm_name: str = "rmappo"     # "rmappo" | "mappo" (feed-forward, mappo/main.py:62-65)
+    # --env_name (mappo/_config.py): "checkers" (ma_gym:Checkers-v0) | "switch" (ma_gym:Switch2-v0, local observations
+    # with the clock: obs_dim 3, 2 agents; episode_length is also the env's max_steps there)
+    env: str = "checkers"
 
     def __post_init__(self):
         if self.algorithm_name not in ("rmappo", "mappo"):
             raise ValueError(f"algorithm_name={self.algorithm_name!r}: expected 'rmappo' or 'mappo'")
+        if self.env not in ("checkers", "switch"):
+            raise ValueError(f"env={self.env!r}: expected 'checkers' or 'switch'")
+        if self.env == "switch" and self.use_centralized_V and self.n_agents != 2:
+            raise ValueError(f"env='switch' with use_centralized_V and n_agents={self.n_agents}: the 3-wide MAPPO "
+                             "kernels are built with a decentralized critic or a centralized one over 2 agents")
 
     @property
     def recurrent(self):
         """The MappoPolicy(recurrent=...) argument of this configuration."""
         return self.algorithm_name != "mappo"
+
+
+def mappo_switch_reference(**kw):
+    """mappo/_config.py pointed at --env_name ma_gym:Switch2-v0: 2 agents, local observations with the clock
+    (obs_dim 3), episode_length = the env's max_steps (100, the reference's --max_step)."""
+    return MappoTrainConfig(**dict(dict(env="switch", n_agents=2, episode_length=100), **kw))
 
 
 @dataclass

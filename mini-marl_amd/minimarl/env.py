@@ -77,6 +77,11 @@ class VecEnv:
             return nxt, rew, done, cur
         return nxt, rew, done
 
+    def step_into(self, act, obs_cur, rew, done, stream):
+        """One auto-resetting step on device pointers (act [E,N] i32, obs_cur [E,N,D], rew [E,N], done [E] u8):
+        no allocation, capturable. The terminal obs is not written."""
+        return lib().mm_env_step(self._h, act, None, obs_cur, rew, done, stream)
+
     def get_state(self):
         """(pos, prev, grid, steps, apples): agent_pos / agent_prev_pos [E,N,2], _full_obs codes [E,R,C]
         (0 empty, 1 lemon, 2 apple, 3 + k agent k), _step_count [E], apples left [E]."""
@@ -174,6 +179,11 @@ class SwitchVecEnv:
         if autoreset:
             return nxt, rew, adone, done, cur
         return nxt, rew, adone, done
+
+    def step_into(self, act, obs_cur, rew, done, stream):
+        """VecEnv.step_into for this env: ``done`` is the env-level all(agent done); the per-agent done list and the
+        terminal obs are not written."""
+        return lib().mm_switch_step(self._h, act, None, obs_cur, rew, None, done, stream)
 
     def get_state(self):
         pos = np.empty((self.E, self.N, 2), np.int32)

@@ -15,7 +15,7 @@ import ctypes
 import torch
 
 from ._lib import MM_MAPPO_ROLLOUT, MappoFwdArgs, check, lib
-from .env import VecEnv, make_env
+from .env import make_env
 from .qnet import ptr, stream_handle
 
 
@@ -55,18 +55,28 @@ class QEvaluator:
 
 
 class MappoEvaluator:
-    """Deterministic episodes of the shared MAPPO actor (MAGYM_Runner.eval)."""
+    """Deterministic episodes of the shared MAPPO actor (MAGYM_Runner.eval) on a dedicated test env: "checkers" or
+    "switch" (local observations with the clock; an env's score stops accumulating at its env-level done)."""
 
-    def __init__(self, n_envs, n_agents, max_steps=100, step_cost=-0.01, device="cuda"):
-        self.env = VecEnv(n_envs, n_agents, max_steps, step_cost, False, device=device)
+    def __init__(self, n_envs, n_agents, max_steps=100, step_cost=-0.01, env="checkers", device="cuda"):
+        self.env = make_env(env, n_envs, n_agents, max_steps, step_cost, False, device=device)
+        self.switch = env == "switch"
         self.E, self.N, self.max_steps = int(n_envs), int(n_agents), int(max_steps)
         self.device = torch.device(device)
+
+    def _step(self, act):
+        out = self.env.step(act)
+        return (out[0], out[1], out[3]) if self.switch else out   # switch: done = all(agent done)
 
     @torch.no_grad()
     def run(self, policy):
         """-> (mean episode reward, per-env episode rewards [E])."""
         E, N, dev, H = self.E, self.N, self.device, policy.H
         R = E * N
+        if policy.D != self.env.obs_dim:
+            raise ValueError(f"policy obs_dim {policy.D} != the test env's obs_dim {self.env.obs_dim}")
+        if policy.cent_agents not in (None, N):
+            raise ValueError(f"policy.cent_agents={policy.cent_agents} != the test env's {N} agents")
         obs = self.env.reset().reshape(R, -1).contiguous()
         ha = torch.zeros(R, H, device=dev)
         ha2 = torch.empty_like(ha)
@@ -82,7 +92,7 @@ class MappoEvaluator:
                 a = policy.rollout_args(obs, logp_out=lp, value_out=v, act_out=act)
                 a.mode, a.deterministic = MM_MAPPO_ROLLOUT, 1
                 policy._fwd(a)
-                nxt, rew, done = self.env.step(act.view(E, N))
+                nxt, rew, done = self._step(act.view(E, N))
                 check(lib().mm_eval_accum(E, N, 0.0, ptr(rew), ptr(done), None, None, ptr(active), ptr(score), None,
                                           stream_handle(dev)), "eval_accum")
                 obs = nxt.reshape(R, -1).contiguous()
@@ -91,7 +101,7 @@ class MappoEvaluator:
             a = policy.rollout_args(obs, ha, hc, None, ha2, hc2, lp, v, act_out=act)
             a.mode, a.deterministic = MM_MAPPO_ROLLOUT, 1
             check(lib().mm_mappo_fwd(ctypes.byref(policy.dims), ctypes.byref(a), stream_handle(dev)), "mappo_fwd")
-            nxt, rew, done = self.env.step(act.view(E, N))
+            nxt, rew, done = self._step(act.view(E, N))
             check(lib().mm_eval_accum(E, N, 0.0, ptr(rew), ptr(done), None, None, ptr(active), ptr(score), None,
                                       stream_handle(dev)), "eval_accum")
             obs = nxt.reshape(R, -1).contiguous()

@@ -17,6 +17,8 @@ torch's CPU randperm stream is not the device's (a recorded one replays through 
 Feed-forward nets (the reference's algorithm_name "mappo", main.py:62-65): MappoPolicy(recurrent=False); the buffer
 then holds no hidden states, the minibatches are slices of a permutation of the T * EN buffer rows
 (feed_forward_generator, shared_buffer.py:159-219) and the kernels are mm_mappo_ff_fwd / _ff_grad / _ff_insert.
+Envs: Checkers (VecEnv, obs_dim 47 | 94) or Switch2 (SwitchVecEnv with local observations and the clock, obs_dim 3;
+critic width 3, or 6 with cent_agents=2); MappoRunner steps either through env.step_into.
 """
 import ctypes
 
@@ -624,8 +626,20 @@ class MappoRunner:
                  grad_allreduce=None, num_mini_batch=1):
         """num_mini_batch: PPO minibatches per epoch (MappoTrainer; their permutations are seeded with ``seed``)."""
         self.env, self.p = env, policy
+        from .env import SwitchVecEnv
+        if isinstance(env, SwitchVecEnv):   # the 3-wide kernels read the own agent's [row, col, clock]
+            switch_cfg = env.cfg
+            if switch_cfg.full_observable:
+                raise ValueError("MappoRunner on Switch needs local observations: full_observable=True (obs_dim "
+                                 f"{env.obs_dim}) has no MAPPO kernel; use_centralized_V gives the critic the env's "
+                                 "joint observation instead (MappoPolicy(cent_agents=n_agents))")
+            if not switch_cfg.clock:
+                raise ValueError("MappoRunner on Switch needs the clock feature: clock=False (obs_dim "
+                                 f"{env.obs_dim}) has no MAPPO kernel (the built width is 3: row, column, clock)")
         if policy.cent_agents not in (None, env.N):
             raise ValueError(f"policy.cent_agents={policy.cent_agents} != the env's {env.N} agents")
+        if policy.D != env.obs_dim:
+            raise ValueError(f"policy obs_dim {policy.D} != the env's obs_dim {env.obs_dim}")
         self.E, self.N, self.D = env.E, env.N, env.obs_dim
         self.T, self.gamma, self.gl = int(T), gamma, gae_lambda
         dev = self.device = policy.device
@@ -657,15 +671,17 @@ class MappoRunner:
         L_, s, b = lib(), stream_handle(self.device), self.buf
         if not self.recurrent:
             self.p._fwd(self.args[t])
-            check(L_.mm_env_step(self.env.handle(), ptr(b.actions[t]), None, ptr(b.obs[t + 1]),
-                                 ptr(b.rewards[t]), ptr(self.done), s), "env_step")
+            check(self.env.step_into(ptr(b.actions[t]), ptr(b.obs[t + 1]), ptr(b.rewards[t]), ptr(self.done), s),
+                  "env_step")
             check(L_.mm_mappo_ff_insert(ptr(self.done), self.N, self.E, ptr(b.masks[t + 1]),
                                         ptr(b.active_masks[t + 1]), ptr(self.counter), s), "mappo_ff_insert")
             return
         check(L_.mm_mappo_fwd(ctypes.byref(self.p.dims), ctypes.byref(self.args[t]), s), "mappo_fwd")
-        # no terminal obs needed (MAPPO bootstraps through masks): only the auto-reset current obs
-        check(L_.mm_env_step(self.env.handle(), ptr(b.actions[t]), None, ptr(b.obs[t + 1]),
-                             ptr(b.rewards[t]), ptr(self.done), s), "env_step")
+        # no terminal obs needed (MAPPO bootstraps through masks): only the auto-reset current obs. On Switch ``done``
+        # is the env-level all(agent done): the reference's insert takes its masks from it and leaves active_masks at
+        # one (magym_runner.py:151-195 builds active_masks but does not pass them on, shared_buffer.py:82-113)
+        check(self.env.step_into(ptr(b.actions[t]), ptr(b.obs[t + 1]), ptr(b.rewards[t]), ptr(self.done), s),
+              "env_step")
         check(L_.mm_mappo_insert(ptr(self.done), self.N, self.p.H, self.E, ptr(b.masks[t + 1]),
                                  ptr(b.active_masks[t + 1]), ptr(b.rnn_states[t + 1]), ptr(b.rnn_states_critic[t + 1]),
                                  ptr(self.counter), s), "mappo_insert")

@@ -1,11 +1,13 @@
 """MAPPO phase timing at BASELINE config 3 (4096 envs x 8 agents, T=100, L=5, 15 PPO epochs).
 
 usage: python tools/mb_mappo.py [--envs E] [--epochs K] [--episodes n] [--centralized-v] [--minibatches M]
-                                [--feed-forward]
+                                [--feed-forward] [--env checkers|switch]
 Prints one JSON line: ms per rollout step, per compute (values + GAE), per train() and per epoch (medians over the
 timed episodes; the first episode is warm-up). --centralized-v: the critic reads the env's share_obs.
 --minibatches M: M PPO minibatches per epoch (num_mini_batch; an epoch is then M updates on 1 / M of the chunks each).
 --feed-forward: the reference's algorithm_name "mappo" (nets without the GRU, minibatches over rows).
+--env switch: the Switch2 corridor env (obs_dim 3; --agents defaults to 2 there, max_steps = T); also prints
+us per rollout step.
 """
 import argparse
 import json
@@ -18,22 +20,25 @@ import minimarl._lib as _L  # noqa: E402
 
 if os.environ.get("MB_LIB"):   # A/B: another build of libminimarl.so
     _L.LIB_PATH = os.path.abspath(os.environ["MB_LIB"])
-from minimarl.env import VecEnv  # noqa: E402
+from minimarl.env import make_env  # noqa: E402
 from minimarl.mappo import MappoPolicy, MappoRunner  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--agents", type=int, default=8)
+    ap.add_argument("--agents", type=int, default=None, help="default: 8 on checkers, 2 on switch")
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--epochs", type=int, default=15)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--centralized-v", action="store_true", help="centralized critic (use_centralized_V)")
     ap.add_argument("--minibatches", type=int, default=1, help="PPO minibatches per epoch (num_mini_batch)")
     ap.add_argument("--feed-forward", action="store_true", help="feed-forward nets (algorithm_name mappo)")
+    ap.add_argument("--env", choices=("checkers", "switch"), default="checkers")
     a = ap.parse_args()
-    env = VecEnv(a.envs, a.agents, max_steps=100, device="cuda")
+    if a.agents is None:
+        a.agents = 2 if a.env == "switch" else 8
+    env = make_env(a.env, a.envs, a.agents, max_steps=a.T if a.env == "switch" else 100, device="cuda")
     p = MappoPolicy(env.obs_dim, 5, 32, "cuda", seed=0, **({"cent_agents": a.agents} if a.centralized_v else {}),
                     **({"recurrent": False} if a.feed_forward else {}))
     r = MappoRunner(env, p, T=a.T, L=5, ppo_epoch=a.epochs, seed=1, num_mini_batch=a.minibatches)
@@ -56,7 +61,8 @@ def main():
     ro, co, tr = (med([x[i] for x in res]) for i in range(3))
     epi = med([sum(x) for x in res])   # (the median episode, not the sum of the phase medians)
     rows = a.envs * a.agents * a.T
-    out = {"envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs, "centralized_v": bool(a.centralized_v),
+    out = {"env": a.env, "obs_dim": env.obs_dim, "rollout_us_per_step": 1e3 * ro / a.T,
+           "envs": a.envs, "agents": a.agents, "T": a.T, "epochs": a.epochs, "centralized_v": bool(a.centralized_v),
            "minibatches": a.minibatches, "feed_forward": bool(a.feed_forward),
            "train_ms_per_update": tr / (a.epochs * a.minibatches),
            "episodes": len(res),
