@@ -16,21 +16,23 @@
 //           j + 32 the others; a LayerNorm sum is one cross-half shuffle. The GRU hidden state stays in
 //           32 registers per lane for all T steps (zero at t = 0, never reset: the reference keeps calling the
 //           policy after done).
-//   env     the in-LDS Checkers step of rollout_env.h (roll_agent_step / roll_obs_word), one lane per env,
-//           agents in id order. The observation is never materialised for the net: LayerNorm 0 and the first
-//           layer's B operands come from the 45-bit observation word and the two coordinates.
+//   env     one lane per env steps it in LDS, agents in id order, between two barriers of the step.
 //   output  every field of a step is one contiguous run per block ([t][e0 .. e0 + ne)[N][X]); the block
 //           writes it thread-linear with 16-byte stores (scalar head / tail where the run is not aligned).
 //
-// Switch (offq_collect_switch_kernel) keeps the block and wave layout, the net from layer 1's bias on, the action
-// draw and the output stores (oc_stage_net / oc_net / oc_act / oc_store are shared), and differs in three places:
-//   obs     three floats per row [row feature, column feature, clock], so layer 1 is one group of 4 k-steps
-//           (features 0..2, the rest zero; its image is 2 KiB, not 12) and LayerNorm 0 is computed from the floats:
-//           mean, centred variance, 1 / sqrt(var + eps).
-//   env     per env in LDS: the agents' cells r << 4 | c, their done flags, the step count and the clock
-//           (float)((double)steps / max_steps), as switch.hip's sw_obs forms it. One lane per env moves the agents
-//           in id order by the rules of oracle/switch.py.
-//   dones   per agent: dones[t, e, n] is agent n's done flag, dones_env[t, e] their conjunction.
+// offq_collect_kernel<Env> is the one episode loop: row bookkeeping, hidden state, the net from layer 1's bias on, the
+// action draw, the barriers and the stores. An env tile gives its argument struct and LDS layout, the staging of the
+// reset state, a row's current observation (the record the stores read and LayerNorm 0's output for the net), the env
+// lane's step with its private episode state, and where dones[t, e, n] comes from:
+//   CheckersTile  the in-LDS step of rollout_env.h (roll_agent_step / roll_obs_word) on nibble-row grids, step and
+//           apple counts in the env lane's registers. The observation (D 47, 24 k-steps of layer 1) is never
+//           materialised for the net: LayerNorm 0 and the first layer's B operands come from the 45-bit
+//           observation word and the two coordinates. dones[t, e, n] is the env's flag.
+//   SwitchTile  per env in LDS: the agents' cells r << 4 | c, their done flags, the step count and the clock, moved
+//           by the rules of switch_dev.h (oracle/switch.py). Three floats per row [row feature, column feature,
+//           clock], so layer 1 is one group of 4 k-steps (features 0..2, the rest zero; its image is 2 KiB, not 12)
+//           and LayerNorm 0 is computed from the floats: mean, centred variance, 1 / sqrt(var + eps).
+//           dones[t, e, n] is agent n's own done flag, dones_env[t, e] their conjunction.
 //
 // The env handle's live state is neither read nor written: every env starts from reset (Checkers: the handle's
 // init_grid / init_pos tables; Switch: the fixed start cells) and the episode's state lives in LDS only.
@@ -332,178 +334,220 @@ __device__ __forceinline__ void oc_act(const OcIo& a, f32x16 qa, bool owner, int
   }
 }
 
-__global__ __launch_bounds__(256) void offq_collect_kernel(OcArgs a) {
+// Checkers tile: nibble-row grids and 16-bit position words in LDS, stepped by rollout_env.h; the env lane keeps the
+// step and apple counts in registers. (Both tiles: float arrays of the LDS layout are used as sm[L::x + i], the
+// members are the integer views.)
+struct CheckersTile {
+  using Args = OcArgs;
   using L = OcLds;
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-  const int N = a.N, R = a.R, C = a.C, gbw = roll_gbw(R);
-  const int e0 = blockIdx.x * a.EB, ne = min(a.EB, a.E - e0), nrows = ne * N;
+  static constexpr int D = OC_D, KS1 = 24;
+  float* sm;
   uint32_t* sgrid = reinterpret_cast<uint32_t*>(sm + L::grid);
-  uint32_t* sinit = reinterpret_cast<uint32_t*>(sm + L::init);
   uint32_t* spos = reinterpret_cast<uint32_t*>(sm + L::pos);
-  int* sact = reinterpret_cast<int*>(sm + L::act);
-  float* srew = sm + L::rew;
-  float* scr = sm + L::cr;
-  float* scc = sm + L::cc;
   uint64_t* sword = reinterpret_cast<uint64_t*>(sm + L::word);
-  float* sq = sm + L::q;
-  float* sdone = sm + L::done;
-  const float* stab = sm + L::stab;
+  int steps = 0, apples = 0;   // the env lane's episode state (lane tid < ne owns env e0 + tid)
 
-  // ---- stage the net and the reset state
-  oc_stage_net<L, OC_D, 24>(sm, a.P);
-  if (tid < R) {
-    sm[L::stab + tid] = a.rtab[tid];
-    uint32_t w = 0;
-    for (int c = 0; c < C; ++c) w |= ((uint32_t)a.init_grid[tid * C + c] & 15u) << (4 * c);
-    sinit[tid] = w;
+  // the coordinate tables and every env's reset state (the handle's init_grid / init_pos); ends behind a barrier
+  __device__ __forceinline__ void stage(const Args& a, int ne, int nrows) {
+    const int tid = threadIdx.x, R = a.R, C = a.C, gbw = roll_gbw(R);
+    uint32_t* sinit = reinterpret_cast<uint32_t*>(sm + L::init);
+    if (tid < R) {
+      sm[L::stab + tid] = a.rtab[tid];
+      uint32_t w = 0;
+      for (int c = 0; c < C; ++c) w |= ((uint32_t)a.init_grid[tid * C + c] & 15u) << (4 * c);
+      sinit[tid] = w;
+    }
+    if (tid < C) sm[L::stab + R + tid] = a.ctab[tid];
+    __syncthreads();
+    for (int i = tid; i < ne * R; i += blockDim.x) {
+      const int le = i / R, r = i - le * R;
+      sgrid[le * gbw + r] = sinit[r];
+    }
+    for (int i = tid; i < nrows; i += blockDim.x) spos[i] = pos16(a.init_pos[i % a.N]);
+    apples = a.init_apples;
+    __syncthreads();
   }
-  if (tid < C) sm[L::stab + R + tid] = a.ctab[tid];
-  __syncthreads();
-  for (int i = tid; i < ne * R; i += blockDim.x) {
-    const int le = i / R, r = i - le * R;
-    sgrid[le * gbw + r] = sinit[r];
-  }
-  for (int i = tid; i < nrows; i += blockDim.x) spos[i] = pos16(a.init_pos[i % N]);
-  __syncthreads();
 
-  // this lane's row of the tile (both lane halves of a row compute its scalars redundantly)
-  const int row = wave * 32 + (lane & 31);
-  const bool valid = row < nrows;
-  const int rle = valid ? row / N : 0, rn = valid ? row - rle * N : 0, rrow = valid ? row : 0;
-  const bool owner = valid && h == 0;
-  const uint64_t rinner = rng_inner((uint64_t)(e0 + rle), (uint64_t)rn);
-  const float eps = *a.eps;
-  const uint64_t c0 = a.counter ? (uint64_t)*a.counter : a.counter0;
-  // the env lane's episode state (lane tid < ne owns env e0 + tid)
-  int steps = 0, apples = a.init_apples;
-  bool edone = false;
-  float ret = 0.0f;
-  f32x16 hid[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) hid[0][r] = hid[1][r] = 0.0f;
-
-  for (int t = 0; t <= a.T; ++t) {
-    // ---- the observation of the current state as a bit word + two coordinates
+  // The current observation of a row (rrow = row, or 0 for a lane past the tile; rle = its env of the tile) as a bit
+  // word + two coordinates: the owner lane leaves that record for the stores, which read it through obs_elem. The
+  // observation is never materialised for the net: x0[s] = feature 2 s + h after LayerNorm 0, straight from the word
+  __device__ __forceinline__ void observe(const Args& a, int row, int rrow, int rle, bool owner, int h,
+                                          float (&x0)[KS1]) {
     const uint32_t pw = spos[rrow];
     const int pr_ = (pw >> 4) & 15, pc_ = pw & 15;
-    const uint64_t wd = roll_obs_word(sgrid + rle * gbw, R, pr_, pc_);
-    const float cr = stab[pr_], cc = stab[R + pc_];
+    const uint64_t wd = roll_obs_word(sgrid + rle * roll_gbw(a.R), a.R, pr_, pc_);
+    const float cr = sm[L::stab + pr_], cc = sm[L::stab + a.R + pc_];
     if (owner) {
       sword[row] = wd;
-      scr[row] = cr;
-      scc[row] = cc;
+      sm[L::cr + row] = cr;
+      sm[L::cc + row] = cc;
     }
-    const int64_t rowbase = ((int64_t)t * a.E + e0) * N;   // row (t, e0, 0) of the [.., E, N, X] fields
-    auto obs_gen = [&](int i) {
-      const int r = i / OC_D, f = i - r * OC_D;
-      return f == 0 ? scr[r] : (f == 1 ? scc[r] : (float)((uint32_t)(sword[r] >> f) & 1u));
-    };
-    if (t == a.T) {
-      lds_sync();
-      oc_store(a.obs, rowbase * OC_D, nrows * OC_D, obs_gen);
-      break;
-    }
-
-    // ---- LayerNorm 0 from the word: 2 coordinates, pc ones, 45 - pc zeros
+    // LayerNorm 0 from the word: 2 coordinates, pc ones, 45 - pc zeros
     const float npc = (float)__popcll(wd);
     const float mu0 = (cr + cc + npc) * (1.0f / OC_D);
     const float dr = cr - mu0, dc = cc - mu0, d1 = 1.0f - mu0;
     const float var0 = (dr * dr + dc * dc + npc * (d1 * d1) + (45.0f - npc) * (mu0 * mu0)) * (1.0f / OC_D);
     const float rs0 = 1.0f / sqrtf(var0 + kLnEps);
-    float x0[24];   // feature 2 s + h, normalised
-    {
-      const uint64_t wh = wd >> h;
+    const uint64_t wh = wd >> h;
 #pragma unroll
-      for (int s4 = 0; s4 < 6; ++s4) {
-        const float4 w4 = *reinterpret_cast<const float4*>(sm + L::ln0w + 24 * h + 4 * s4);
-        const float4 b4 = *reinterpret_cast<const float4*>(sm + L::ln0b + 24 * h + 4 * s4);
-        const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+    for (int s4 = 0; s4 < 6; ++s4) {
+      const float4 w4 = *reinterpret_cast<const float4*>(sm + L::ln0w + 24 * h + 4 * s4);
+      const float4 b4 = *reinterpret_cast<const float4*>(sm + L::ln0b + 24 * h + 4 * s4);
+      const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-        for (int si = 0; si < 4; ++si) {
-          const int s = 4 * s4 + si;
-          const float xv = s == 0 ? (h ? cc : cr) : (float)((uint32_t)(wh >> (2 * s)) & 1u);
-          x0[s] = (xv - mu0) * rs0 * wv[si] + bv[si];
-        }
+      for (int si = 0; si < 4; ++si) {
+        const int s = 4 * s4 + si;
+        const float xv = s == 0 ? (h ? cc : cr) : (float)((uint32_t)(wh >> (2 * s)) & 1u);
+        x0[s] = (xv - mu0) * rs0 * wv[si] + bv[si];
       }
     }
-    const f32x16 qa = oc_net<L, 24>(sm, x0, hid, lane, h);
-    oc_act(a, qa, owner, row, c0 + (uint64_t)t, rinner, eps, sact, sq);
-    lds_sync();
-
-    // ---- env step: one lane per env, agents in id order; a finished env is not stepped
-    if (tid < ne) {
-      uint32_t* rows = sgrid + tid * gbw;
-      if (!edone) {
-        float sum = 0.0f;
-#pragma unroll 1
-        for (int k = 0; k < N; ++k) {
-          const RollMove mv = roll_agent_step(spos[tid * N + k], sact[tid * N + k], k, rows, R, C, a.step_cost);
-          spos[tid * N + k] = mv.w;
-          srew[tid * N + k] = mv.rew;
-          apples -= mv.ate ? 1 : 0;
-          sum = k == 0 ? mv.rew : sum + mv.rew;
-        }
-        if (a.common)
-          for (int k = 0; k < N; ++k) srew[tid * N + k] = sum;
-        ++steps;
-        edone = steps >= a.max_steps || apples == 0;
-      } else {
-        for (int k = 0; k < N; ++k) srew[tid * N + k] = 0.0f;
-      }
-      sdone[tid] = edone ? 1.0f : 0.0f;
-      ret += srew[tid * N];
-    }
-    lds_sync();
-
-    // ---- the step's episode fields
-    oc_store(a.obs, rowbase * OC_D, nrows * OC_D, obs_gen);
-    oc_store(a.acts, rowbase * OC_A, nrows * OC_A, [&](int i) {
-      const int r = i / OC_A;
-      return sact[r] == i - r * OC_A ? 1.0f : 0.0f;
-    });
-    oc_store(a.rew, rowbase, nrows, [&](int i) { return srew[i]; });
-    oc_store(a.dones, rowbase, nrows, [&](int i) { return sdone[i / N]; });
-    oc_store(a.dones_env, (int64_t)t * a.E + e0, ne, [&](int i) { return sdone[i]; });
-    if (a.q_out) oc_store(a.q_out, rowbase * OC_A, nrows * OC_A, [&](int i) { return sq[i]; });
-    lds_sync();
   }
-  if (a.ret_out && tid < ne) a.ret_out[e0 + tid] = ret;
-}
 
-__global__ __launch_bounds__(256) void offq_collect_switch_kernel(OsArgs a) {
+  // element i of the tile's [rows][D] observations
+  __device__ __forceinline__ float obs_elem(int i) const {
+    const int r = i / OC_D, f = i - r * OC_D;
+    return f == 0 ? sm[L::cr + r] : (f == 1 ? sm[L::cc + r] : (float)((uint32_t)(sword[r] >> f) & 1u));
+  }
+
+  // The env lane steps env le of the tile, agents in id order: each agent's own reward into srew, their agent-order
+  // sum into sum; returns whether the env is now done
+  __device__ __forceinline__ bool step(const Args& a, int le, const int* sact, float* srew, float& sum) {
+    const int N = a.N;
+    uint32_t* rows = sgrid + le * roll_gbw(a.R);
+#pragma unroll 1
+    for (int k = 0; k < N; ++k) {
+      const RollMove mv = roll_agent_step(spos[le * N + k], sact[le * N + k], k, rows, a.R, a.C, a.step_cost);
+      spos[le * N + k] = mv.w;
+      srew[le * N + k] = mv.rew;
+      apples -= mv.ate ? 1 : 0;
+      sum = k == 0 ? mv.rew : sum + mv.rew;
+    }
+    ++steps;
+    return steps >= a.max_steps || apples == 0;
+  }
+
+  // dones[t, e, n] of tile row i: Checkers agents have no done flag of their own, so the env's
+  __device__ __forceinline__ float agent_done(const Args& a, int i) const { return sm[L::done + i / a.N]; }
+};
+
+// Switch tile: per env in LDS the agents' cells r << 4 | c, their done flags (0 / 1 as floats: they are the dones
+// field), the step count and the clock of the current state, stepped by the rules of switch_dev.h
+struct SwitchTile {
+  using Args = OsArgs;
   using L = OsLds;
+  static constexpr int D = OS_D, KS1 = 4;
+  float* sm;
+  uint32_t* spos = reinterpret_cast<uint32_t*>(sm + L::pos);
+  int* ssteps = reinterpret_cast<int*>(sm + L::steps);
+
+  // the feature tables and every env's reset state (the agents' start cells, step 0); ends behind a barrier
+  __device__ __forceinline__ void stage(const Args& a, int ne, int nrows) {
+    const int tid = threadIdx.x;
+    if (tid < 3) sm[L::stab + tid] = a.tab.row[tid];
+    if (tid < 7) sm[L::stab + 4 + tid] = a.tab.col[tid];
+    for (int i = tid; i < nrows; i += blockDim.x) {
+      const int k = i % a.N;
+      spos[i] = (uint32_t)(sw_home_row(k) << 4 | sw_start_col(k));
+      sm[L::adone + i] = 0.0f;
+    }
+    if (tid < ne) {
+      ssteps[tid] = 0;
+      sm[L::clk + tid] = 0.0f;
+    }
+    __syncthreads();
+  }
+
+  // As CheckersTile::observe; the record is the observation itself: row feature, column feature, clock
+  __device__ __forceinline__ void observe(const Args&, int row, int rrow, int rle, bool owner, int h,
+                                          float (&x0)[KS1]) {
+    const uint32_t pw = spos[rrow];
+    const float cr = sm[L::stab + ((pw >> 4) & 3)], cc = sm[L::stab + 4 + (pw & 7)], ck = sm[L::clk + rle];
+    if (owner) {
+      sm[L::cr + row] = cr;
+      sm[L::cc + row] = cc;
+      sm[L::ck + row] = ck;
+    }
+    // LayerNorm 0 over the three floats: mean, centred variance. Lane half h feeds features h and 2 + h (feature 3 is
+    // a zero pad: its LayerNorm weight, bias and W1 column are staged as zero)
+    const float mu0 = ((cr + cc) + ck) / (float)OS_D;
+    const float dr = cr - mu0, dc = cc - mu0, dk = ck - mu0;
+    const float var0 = (dr * dr + dc * dc + dk * dk) / (float)OS_D;
+    const float rs0 = 1.0f / sqrtf(var0 + kLnEps);
+    const float4 w4 = *reinterpret_cast<const float4*>(sm + L::ln0w + 4 * h);
+    const float4 b4 = *reinterpret_cast<const float4*>(sm + L::ln0b + 4 * h);
+    x0[0] = (h ? dc : dr) * rs0 * w4.x + b4.x;
+    x0[1] = (h ? 0.0f : dk) * rs0 * w4.y + b4.y;
+    x0[2] = 0.0f;
+    x0[3] = 0.0f;
+  }
+
+  __device__ __forceinline__ float obs_elem(int i) const {
+    const int r = i / OS_D, f = i - r * OS_D;
+    return sm[(f == 0 ? L::cr : (f == 1 ? L::cc : L::ck)) + r];
+  }
+
+  // As CheckersTile::step, by oracle/switch.py SwitchOracle.step: the moves act on the cells in LDS, so a move sees
+  // the cells as updated so far this step
+  __device__ __forceinline__ bool step(const Args& a, int le, const int* sact, float* srew, float& sum) {
+    const int N = a.N, b = le * N, steps = ssteps[le] + 1;
+    const bool timeout = steps >= a.max_steps;
+    float* sadone = sm + L::adone;
+    bool all = true;
+#pragma unroll 1
+    for (int k = 0; k < N; ++k) {
+      bool ad = sadone[b + k] != 0.0f;
+      float rw = a.step_cost;
+      if (!ad) {   // a finished agent keeps its cell and goes on receiving step_cost
+        const uint32_t cw = spos[b + k];
+        int r = (int)(cw >> 4), c = (int)(cw & 15);
+        const SwMove m = sw_move(r, c, sact[b + k]);
+        const uint32_t nw = (uint32_t)(m.r << 4 | m.c);
+        bool ok = m.open;   // and no other agent, finished or not, holds the cell
+        for (int j = 0; j < N; ++j) ok = ok && (j == k || spos[b + j] != nw);
+        if (ok) {
+          spos[b + k] = nw;
+          r = m.r;
+          c = m.c;
+        }
+        if (sw_at_target(k, r, c)) {
+          ad = true;
+          rw = kSwTargetReward;
+        }
+      }
+      ad = ad || timeout;
+      sadone[b + k] = ad ? 1.0f : 0.0f;
+      srew[b + k] = rw;
+      sum = k == 0 ? rw : sum + rw;
+      all = all && ad;
+    }
+    ssteps[le] = steps;
+    sm[L::clk + le] = sw_clock(steps, a.max_steps);
+    return all;
+  }
+
+  // dones[t, e, n] of tile row i: agent n's own flag
+  __device__ __forceinline__ float agent_done(const Args&, int i) const { return sm[L::adone + i]; }
+};
+
+// The episode loop, for either tile. Per step: observe, [t = T: store the final observation and stop,] net, action
+// draw | barrier | env step by the env lanes | barrier | the step's stores | barrier.
+template <class Env>
+__global__ __launch_bounds__(256) void offq_collect_kernel(typename Env::Args a) {
+  using L = typename Env::L;
+  constexpr int D = Env::D, KS1 = Env::KS1;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
   const int N = a.N;
   const int e0 = blockIdx.x * a.EB, ne = min(a.EB, a.E - e0), nrows = ne * N;
-  uint32_t* spos = reinterpret_cast<uint32_t*>(sm + L::pos);
-  float* sadone = sm + L::adone;
   int* sact = reinterpret_cast<int*>(sm + L::act);
   float* srew = sm + L::rew;
-  float* scr = sm + L::cr;
-  float* scc = sm + L::cc;
-  float* sck = sm + L::ck;
   float* sq = sm + L::q;
-  int* ssteps = reinterpret_cast<int*>(sm + L::steps);
-  float* sclk = sm + L::clk;
   float* sdone = sm + L::done;
-  const float* stab = sm + L::stab;
+  Env env{sm};
 
-  // ---- stage the net and the reset state: agent k starts at (0, 1) (0, 5) (2, 1) (2, 5)[k], step 0
-  oc_stage_net<L, OS_D, 4>(sm, a.P);
-  if (tid < 3) sm[L::stab + tid] = a.tab.row[tid];
-  if (tid < 7) sm[L::stab + 4 + tid] = a.tab.col[tid];
-  for (int i = tid; i < nrows; i += blockDim.x) {
-    const int k = i % N;
-    spos[i] = (uint32_t)((k < 2 ? 0 : 2) << 4 | ((k & 1) ? 5 : 1));
-    sadone[i] = 0.0f;
-  }
-  if (tid < ne) {
-    ssteps[tid] = 0;
-    sclk[tid] = 0.0f;
-  }
-  __syncthreads();
+  // ---- stage the net and the reset state
+  oc_stage_net<L, D, KS1>(sm, a.P);
+  env.stage(a, ne, nrows);
 
   // this lane's row of the tile (both lane halves of a row compute its scalars redundantly)
   const int row = wave * 32 + (lane & 31);
@@ -520,104 +564,43 @@ __global__ __launch_bounds__(256) void offq_collect_switch_kernel(OsArgs a) {
   for (int r = 0; r < 16; ++r) hid[0][r] = hid[1][r] = 0.0f;
 
   for (int t = 0; t <= a.T; ++t) {
-    // ---- the observation of the current state: row feature, column feature, clock
-    const uint32_t pw = spos[rrow];
-    const float cr = stab[(pw >> 4) & 3], cc = stab[4 + (pw & 7)], ck = sclk[rle];
-    if (owner) {
-      scr[row] = cr;
-      scc[row] = cc;
-      sck[row] = ck;
-    }
+    float x0[KS1];   // LayerNorm 0's output: this lane's feature 2 s + h
+    env.observe(a, row, rrow, rle, owner, h, x0);
     const int64_t rowbase = ((int64_t)t * a.E + e0) * N;   // row (t, e0, 0) of the [.., E, N, X] fields
-    auto obs_gen = [&](int i) {
-      const int r = i / OS_D, f = i - r * OS_D;
-      return f == 0 ? scr[r] : (f == 1 ? scc[r] : sck[r]);
-    };
+    auto obs_gen = [&](int i) { return env.obs_elem(i); };
     if (t == a.T) {
       lds_sync();
-      oc_store(a.obs, rowbase * OS_D, nrows * OS_D, obs_gen);
+      oc_store(a.obs, rowbase * D, nrows * D, obs_gen);
       break;
     }
 
-    // ---- LayerNorm 0 over the three floats: mean, centred variance. Lane half h feeds features h and 2 + h
-    // (feature 3 is a zero pad: its LayerNorm weight, bias and W1 column are staged as zero)
-    const float mu0 = ((cr + cc) + ck) / (float)OS_D;
-    const float dr = cr - mu0, dc = cc - mu0, dk = ck - mu0;
-    const float var0 = (dr * dr + dc * dc + dk * dk) / (float)OS_D;
-    const float rs0 = 1.0f / sqrtf(var0 + kLnEps);
-    float x0[4];   // feature 2 s + h, normalised
-    {
-      const float4 w4 = *reinterpret_cast<const float4*>(sm + L::ln0w + 4 * h);
-      const float4 b4 = *reinterpret_cast<const float4*>(sm + L::ln0b + 4 * h);
-      x0[0] = (h ? dc : dr) * rs0 * w4.x + b4.x;
-      x0[1] = (h ? 0.0f : dk) * rs0 * w4.y + b4.y;
-      x0[2] = 0.0f;
-      x0[3] = 0.0f;
-    }
-    const f32x16 qa = oc_net<L, 4>(sm, x0, hid, lane, h);
+    const f32x16 qa = oc_net<L, KS1>(sm, x0, hid, lane, h);
     oc_act(a, qa, owner, row, c0 + (uint64_t)t, rinner, eps, sact, sq);
     lds_sync();
 
-    // ---- env step (oracle/switch.py SwitchOracle.step): one lane per env, agents in id order on the cells in LDS,
-    // so a move sees the cells as updated so far this step; a finished env is not stepped
+    // ---- env step: one lane per env; a finished env is not stepped
     if (tid < ne) {
-      const int b = tid * N;
       if (!edone) {
-        const int steps = ssteps[tid] + 1;
-        const bool timeout = steps >= a.max_steps;
-        bool all = true;
         float sum = 0.0f;
-#pragma unroll 1
-        for (int k = 0; k < N; ++k) {
-          bool ad = sadone[b + k] != 0.0f;
-          float rw = a.step_cost;
-          if (!ad) {   // a finished agent keeps its cell and goes on receiving step_cost
-            const uint32_t cw = spos[b + k];
-            int r = (int)(cw >> 4), c = (int)(cw & 15);
-            const int act = sact[b + k];   // 0 down, 1 left, 2 up, 3 right, 4 noop
-            if (act < 4) {
-              const int nr = r + (act == 0) - (act == 2), nc = c + (act == 3) - (act == 1);
-              bool ok = sw_open(nr, nc);
-              const uint32_t nw = ok ? (uint32_t)(nr << 4 | nc) : 0u;
-              for (int j = 0; j < N; ++j) ok = ok && (j == k || spos[b + j] != nw);
-              if (ok) {
-                spos[b + k] = nw;
-                r = nr;
-                c = nc;
-              }
-            }
-            if (r == (k < 2 ? 0 : 2) && c == ((k & 1) ? 0 : 6)) {   // targets (0, 6) (0, 0) (2, 6) (2, 0)
-              ad = true;
-              rw = 5.0f;
-            }
-          }
-          ad = ad || timeout;
-          sadone[b + k] = ad ? 1.0f : 0.0f;
-          srew[b + k] = rw;
-          sum = k == 0 ? rw : sum + rw;
-          all = all && ad;
-        }
+        edone = env.step(a, tid, sact, srew, sum);
         if (a.common)
-          for (int k = 0; k < N; ++k) srew[b + k] = sum;
-        ssteps[tid] = steps;
-        sclk[tid] = (float)((double)steps / (double)a.max_steps);
-        edone = all;
+          for (int k = 0; k < N; ++k) srew[tid * N + k] = sum;
       } else {
-        for (int k = 0; k < N; ++k) srew[b + k] = 0.0f;
+        for (int k = 0; k < N; ++k) srew[tid * N + k] = 0.0f;
       }
       sdone[tid] = edone ? 1.0f : 0.0f;
-      ret += srew[b];
+      ret += srew[tid * N];
     }
     lds_sync();
 
     // ---- the step's episode fields
-    oc_store(a.obs, rowbase * OS_D, nrows * OS_D, obs_gen);
+    oc_store(a.obs, rowbase * D, nrows * D, obs_gen);
     oc_store(a.acts, rowbase * OC_A, nrows * OC_A, [&](int i) {
       const int r = i / OC_A;
       return sact[r] == i - r * OC_A ? 1.0f : 0.0f;
     });
     oc_store(a.rew, rowbase, nrows, [&](int i) { return srew[i]; });
-    oc_store(a.dones, rowbase, nrows, [&](int i) { return sadone[i]; });
+    oc_store(a.dones, rowbase, nrows, [&](int i) { return env.agent_done(a, i); });
     oc_store(a.dones_env, (int64_t)t * a.E + e0, ne, [&](int i) { return sdone[i]; });
     if (a.q_out) oc_store(a.q_out, rowbase * OC_A, nrows * OC_A, [&](int i) { return sq[i]; });
     lds_sync();
@@ -706,6 +689,19 @@ int fill_io(OcIo& a, const char* who, const float* P, const mm_offq_collect_io* 
   return MM_OK;
 }
 
+// the launch of a tile's kernel: its dynamic-LDS attribute (set once per process), one block per EB envs
+template <class Env>
+int launch_collect(const typename Env::Args& a, int64_t n_envs, hipStream_t s) {
+  constexpr int lds = Env::L::total * 4;
+  static const hipError_t set_lds_attribute =
+      hipFuncSetAttribute((const void*)offq_collect_kernel<Env>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  MM_HIP_CHECK(set_lds_attribute);
+  const unsigned nb = (unsigned)((n_envs + a.EB - 1) / a.EB);
+  hipLaunchKernelGGL(offq_collect_kernel<Env>, dim3(nb), dim3(256), lds, s, a);
+  MM_HIP_CHECK(hipGetLastError());
+  return MM_OK;
+}
+
 }  // namespace
 }  // namespace mm
 
@@ -724,12 +720,6 @@ int mm_offq_collect(mm_env* env, const mm_offq_dims* d, const float* P, const mm
   OcArgs a;
   rc = fill_io(a, "offq_collect", P, io, n_envs, T, ev.N, ev.max_steps, ev.step_cost);
   if (rc) return rc;
-  constexpr int lds = OcLds::total * 4;
-  static const int attr_rc = [&]() -> int {
-    MM_HIP_CHECK(hipFuncSetAttribute((const void*)offq_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return MM_OK;
-  }();
-  if (attr_rc != MM_OK) return attr_rc;
   a.init_grid = ev.init_grid;
   a.init_pos = ev.init_pos;
   a.rtab = ev.rtab;
@@ -737,10 +727,7 @@ int mm_offq_collect(mm_env* env, const mm_offq_dims* d, const float* P, const mm
   a.R = ev.R;
   a.C = ev.C;
   a.init_apples = ev.init_apples;
-  const unsigned nb = (unsigned)((n_envs + a.EB - 1) / a.EB);
-  hipLaunchKernelGGL(offq_collect_kernel, dim3(nb), dim3(256), lds, (hipStream_t)s, a);
-  MM_HIP_CHECK(hipGetLastError());
-  return MM_OK;
+  return launch_collect<CheckersTile>(a, n_envs, (hipStream_t)s);
 }
 
 int mm_offq_collect_switch_supported(const mm_switch* env, const mm_offq_dims* d, int64_t n_envs, int32_t T) {
@@ -756,18 +743,8 @@ int mm_offq_collect_switch(mm_switch* env, const mm_offq_dims* d, const float* P
   OsArgs a;
   rc = fill_io(a, "offq_collect_switch", P, io, n_envs, T, c.n_agents, c.max_steps, c.step_cost);
   if (rc) return rc;
-  constexpr int lds = OsLds::total * 4;
-  static const int attr_rc = [&]() -> int {
-    MM_HIP_CHECK(
-        hipFuncSetAttribute((const void*)offq_collect_switch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return MM_OK;
-  }();
-  if (attr_rc != MM_OK) return attr_rc;
   a.tab = env->tab;
-  const unsigned nb = (unsigned)((n_envs + a.EB - 1) / a.EB);
-  hipLaunchKernelGGL(offq_collect_switch_kernel, dim3(nb), dim3(256), lds, (hipStream_t)s, a);
-  MM_HIP_CHECK(hipGetLastError());
-  return MM_OK;
+  return launch_collect<SwitchTile>(a, n_envs, (hipStream_t)s);
 }
 
 }  // extern "C"

@@ -22,10 +22,9 @@ static SwitchTab switch_tables() {
 }
 
 __device__ __forceinline__ void sw_init(SwitchState& s, int N) {
-  const int8_t ir[4] = {0, 0, 2, 2}, ic[4] = {1, 5, 1, 5};
   for (int k = 0; k < 4; ++k) {
-    s.pos[k][0] = k < N ? ir[k] : -1;
-    s.pos[k][1] = k < N ? ic[k] : -1;
+    s.pos[k][0] = (int8_t)(k < N ? sw_home_row(k) : -1);
+    s.pos[k][1] = (int8_t)(k < N ? sw_start_col(k) : -1);
     s.adone[k] = 0;
   }
   s.steps = 0;
@@ -33,17 +32,10 @@ __device__ __forceinline__ void sw_init(SwitchState& s, int N) {
 
 __device__ __forceinline__ void sw_obs(const SwitchTab& tab, const SwitchState& s, int N, int max_steps, int full,
                                        int clock, float* __restrict__ out) {
-  const int ld = 2 + clock;
-  const int D = full ? ld * N : ld;
-  const float clk = (float)((double)s.steps / (double)max_steps);
+  const float clk = sw_clock(s.steps, max_steps);
   for (int k = 0; k < N; ++k) {
-    float loc[3] = {tab.row[s.pos[k][0]], tab.col[s.pos[k][1]], clk};
-    if (full) {
-      for (int j = 0; j < N; ++j)
-        for (int f = 0; f < ld; ++f) out[j * D + k * ld + f] = loc[f];
-    } else {
-      for (int f = 0; f < ld; ++f) out[k * D + f] = loc[f];
-    }
+    const float loc[3] = {tab.row[s.pos[k][0]], tab.col[s.pos[k][1]], clk};
+    sw_write_local(out, k, N, 2 + clock, full, loc);
   }
 }
 
@@ -147,18 +139,15 @@ __global__ __launch_bounds__(256) void switch_step_kernel(SwitchTab tab, SwitchS
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     if (j >= N || s.adone[j]) continue;
-    const int aj = a[j];
-    if (aj >= 0 && aj < 4) {   // 0 down, 1 left, 2 up, 3 right
-      const int r = s.pos[j][0] + (aj == 0) - (aj == 2), c = s.pos[j][1] + (aj == 3) - (aj == 1);
-      bool ok = sw_open(r, c);
+    const SwMove m = sw_move(s.pos[j][0], s.pos[j][1], a[j]);
+    bool ok = m.open;   // and no other agent, finished or not, holds the cell
 #pragma unroll
-      for (int i = 0; i < NP; ++i) ok = ok && (i >= N || i == j || s.pos[i][0] != r || s.pos[i][1] != c);
-      if (ok) {
-        s.pos[j][0] = (int8_t)r;
-        s.pos[j][1] = (int8_t)c;
-      }
+    for (int i = 0; i < NP; ++i) ok = ok && (i >= N || i == j || s.pos[i][0] != m.r || s.pos[i][1] != m.c);
+    if (ok) {
+      s.pos[j][0] = (int8_t)m.r;
+      s.pos[j][1] = (int8_t)m.c;
     }
-    if (s.pos[j][0] == (j < 2 ? 0 : 2) && s.pos[j][1] == ((j & 1) ? 0 : 6)) {   // targets (0,6) (0,0) (2,6) (2,0)
+    if (sw_at_target(j, s.pos[j][0], s.pos[j][1])) {
       s.adone[j] = 1;
       if (j == k) reached = true;
     }
@@ -193,19 +182,10 @@ __global__ __launch_bounds__(256) void switch_step_kernel(SwitchTab tab, SwitchS
     for (int f = 0; f < D; ++f) dp[k * D + f] = sp[k * D + f];
   }
   if (ag) {
-    rew[e * N + k] = reached ? 5.0f : step_cost;
+    rew[e * N + k] = reached ? kSwTargetReward : step_cost;
     if (agent_done) agent_done[e * N + k] = my_done ? 1 : 0;
-    const float clk = (float)((double)s.steps / (double)max_steps);
-    const float loc[3] = {tab.row[my_r], tab.col[my_c], clk};
-    if (next_obs) {
-      float* o = next_obs + srow * next_se;
-      if (full) {
-        for (int j = 0; j < N; ++j)
-          for (int f = 0; f < ld; ++f) o[j * D + k * ld + f] = loc[f];
-      } else {
-        for (int f = 0; f < ld; ++f) o[k * D + f] = loc[f];
-      }
-    }
+    const float loc[3] = {tab.row[my_r], tab.col[my_c], sw_clock(s.steps, max_steps)};
+    if (next_obs) sw_write_local(next_obs + srow * next_se, k, N, ld, full, loc);
   }
   const bool autoreset = obs_cur || cur_row;
   if (env_ok && k == 0) {
@@ -215,17 +195,10 @@ __global__ __launch_bounds__(256) void switch_step_kernel(SwitchTab tab, SwitchS
     st[e] = s;
   }
   if (obs_cur && ag) {          // the next current obs: the reset obs where the env finished
-    // a finished env restarts at the agents' initial cells, step 0: (0,1) (0,5) (2,1) (2,5)
-    const int r0 = all ? (k < 2 ? 0 : 2) : my_r, c0 = all ? ((k & 1) ? 5 : 1) : my_c;
-    const float clk = all ? 0.0f : (float)((double)s.steps / (double)max_steps);
-    const float loc[3] = {tab.row[r0], tab.col[c0], clk};
-    float* o = obs_cur + e * N * D;
-    if (full) {
-      for (int j = 0; j < N; ++j)
-        for (int f = 0; f < ld; ++f) o[j * D + k * ld + f] = loc[f];
-    } else {
-      for (int f = 0; f < ld; ++f) o[k * D + f] = loc[f];
-    }
+    // a finished env restarts at the agents' start cells, step 0
+    const int r0 = all ? sw_home_row(k) : my_r, c0 = all ? sw_start_col(k) : my_c;
+    const float loc[3] = {tab.row[r0], tab.col[c0], all ? 0.0f : sw_clock(s.steps, max_steps)};
+    sw_write_local(obs_cur + e * N * D, k, N, ld, full, loc);
   }
 }
 
