@@ -23,6 +23,7 @@
  *   mm_mappo_grad        (fused: forward recompute + BPTT + weight grads of one epoch, same lines)
  *   mm_mappo_gae, insert SharedReplayBuffer.compute_returns/insert   mappo/runner/shared/shared_buffer.py:82-157
  *   mm_offq_*            offpolicy QMix.train_policy_on_batch etc.   offpolicy/algorithms/qmix/qmix.py:80-226
+ *   mm_moffq_*           offpolicy M_QMix.train_policy_on_batch (feed-forward, transition batches)  offpolicy/algorithms/mqmix/mqmix.py:68-218
  *   mm_erb_*             PrioritizedRecReplayBuffer / RecReplayBuffer offpolicy/utils/rec_buffer.py:10-324; segment_tree.py:18-165
  *   mm_eval_accum        greedy test loops                           vdn/_test.py:22-50; magym_runner.py:198-241
  */
@@ -799,6 +800,36 @@ int mm_offq_q_values(const mm_offq_dims* d, const float* P, const float* obs, co
                      int32_t L, int64_t R, void* ws, int64_t ws_bytes, mm_stream_t s);
 /* soft_update: target <- target * (1 - tau) + source * tau over n floats (tau = 1: hard update). */
 int mm_offq_soft_update(float* target, const float* source, int64_t n, double tau, mm_stream_t s);
+/* ------------------------------------------------------------------ offpolicy feed-forward QMix / VDN ("mqmix" / "mvdn")
+ * Replaces M_QMix.train_policy_on_batch (offpolicy/algorithms/mqmix/mqmix.py:68-218) with M_QMixPolicy
+ * (algorithm/mQMixPolicy.py:35-113): the QMixer / VDN mixer of mm_offq_* over a feed-forward agent net
+ * LN(D) -> [Linear, ReLU, LN] x 2 -> Linear(A), trained on batches of single transitions (csrc/moffq.hip).
+ * Parameters: exactly the flat [agent | mixer] vector of mm_offq_* (mm_offq_param_counts, mm_offq_mixer_offsets;
+ * mm_clip_adam and mm_offq_soft_update apply unchanged); the six recurrent tensors Wih Whh bih bhh lnr_w lnr_b are
+ * not read and get exactly zero gradient. Batch = MlpReplayBuffer.sample layout: obs / nobs [N, B, D] (row n B + b),
+ * cent_obs / cent_nobs [B, S] (NULL for VDN), acts one-hot [N, B, A] (index = first maximum), rewards [N, B]
+ * (agent 0's are used), dones_env [B], is_weight [B] (NULL: no PER). loss = mean_b w_b f(Q_tot - target),
+ * f = e^2 or Huber; priorities |err| + per_eps. Supported: H = 64, A = 5, D in {3, 47, 94}, N >= 1, B >= 1; QMIX with
+ * hypernet_layers = 2, K <= MM_OFFQ_MAX_MIXER_HIDDEN, N*K <= 4096, any S; or VDN. Anything else: MM_EINVAL (-1 from
+ * the size query) before any launch. Not built: use_popart, available-action masks, multidiscrete actions,
+ * layer_N != 1, hypernet_layers = 1, use_conv1d, weight_decay. */
+typedef struct mm_moffq_batch {
+  const float* obs; const float* nobs; const float* cent_obs; const float* cent_nobs; const float* acts;
+  const float* rewards; const float* dones_env; const float* is_weight;
+  int32_t B;
+  int32_t double_q, huber;
+  float gamma, huber_delta, per_eps;
+} mm_moffq_batch;
+int64_t mm_moffq_workspace_bytes(const mm_offq_dims* d, int32_t B);
+/* Two launches: one fused kernel (both agent nets, both mixers, loss, backward, per-block weight-gradient partials
+ * over tiles of 16 transitions) and a fixed-order reduction into grad [agent | mixer], stats float[2] = loss, Q_tot
+ * mean. priorities [B] is written under PER only (may be NULL otherwise). ws: device scratch of
+ * mm_moffq_workspace_bytes(d, B), needs no initialisation. Same inputs give the same bits. Follow with mm_clip_adam. */
+int mm_moffq_loss_grad(const mm_offq_dims* d, const mm_moffq_batch* b, const float* P, const float* PT, float* grad,
+                       void* ws, int64_t ws_bytes, float* stats, float* priorities, mm_stream_t s);
+/* get_q_values: obs [R, D] -> q [R, A], or with actions (int32 [R], may be NULL) q [R] = Q(obs_r, actions_r). */
+int mm_moffq_q_values(const mm_offq_dims* d, const float* P, const float* obs, const int32_t* actions, float* q,
+                      int64_t R, mm_stream_t s);
 /* Episode collector (RecRunner.collect_rollout, offpolicy/runner/shared/magym_runner.py:40-141, for E lockstep
  * Checkers envs): ONE launch runs a whole T-step episode of every env from reset with the behavior agent net P
  * (hidden zero at t = 0, carried over all T steps, not reset at done) and per-(env, agent) epsilon-greedy:

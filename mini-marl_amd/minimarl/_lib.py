@@ -380,6 +380,20 @@ _SIGS += [
 ]
 
 
+class MoffqBatch(ctypes.Structure):
+    """mm_moffq_batch (include/minimarl.h)"""
+    _fields_ = [("obs", c_vp), ("nobs", c_vp), ("cent_obs", c_vp), ("cent_nobs", c_vp), ("acts", c_vp),
+                ("rewards", c_vp), ("dones_env", c_vp), ("is_weight", c_vp), ("B", c_i32), ("double_q", c_i32),
+                ("huber", c_i32), ("gamma", c_f32), ("huber_delta", c_f32), ("per_eps", c_f32)]
+
+
+_SIGS += [
+    ("mm_moffq_workspace_bytes", c_i64, [_OD, c_i32]),
+    ("mm_moffq_loss_grad", c_i32, [_OD, ctypes.POINTER(MoffqBatch), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    ("mm_moffq_q_values", c_i32, [_OD, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+]
+
+
 class OffqCollectIO(ctypes.Structure):
     """mm_offq_collect_io (include/minimarl.h)"""
     _fields_ = [("eps", c_vp), ("counter", c_vp), ("counter0", c_u64), ("seed", c_u64), ("common_reward", c_i32),
