@@ -25,6 +25,8 @@
  *   mm_offq_*            offpolicy QMix.train_policy_on_batch etc.   offpolicy/algorithms/qmix/qmix.py:80-226
  *   mm_moffq_*           offpolicy M_QMix.train_policy_on_batch (feed-forward, transition batches)  offpolicy/algorithms/mqmix/mqmix.py:68-218
  *   mm_erb_*             PrioritizedRecReplayBuffer / RecReplayBuffer offpolicy/utils/rec_buffer.py:10-324; segment_tree.py:18-165
+ *   mm_moffq_collect*    the MLP runner's collect loop for mqmix / mvdn: a window of transitions in one launch
+ *   mm_mlpbuf_*          PrioritizedMlpReplayBuffer / MlpReplayBuffer offpolicy/utils/mlp_buffer.py:10-340
  *   mm_eval_accum        greedy test loops                           vdn/_test.py:22-50; magym_runner.py:198-241
  */
 #ifndef MINIMARL_H
@@ -968,6 +970,82 @@ int32_t* mm_erb_error_word(mm_erb* b);        /* device i32 [1]: bit 0 bad updat
                                                  bit 2 bad gather index */
 /* Stream-ordered device copies of the trees, max_priority and the error word (any may be NULL). */
 int mm_erb_copy_state(mm_erb* b, double* sum_dst, double* min_dst, float* maxp_dst, int32_t* err_dst, mm_stream_t s);
+
+/* ------------------------------------------------------- offpolicy transition collector (mm_moffq_collect*) */
+/* Feed-forward transition collector for mqmix / mvdn (csrc/moffq_collect.hip): ONE launch runs a window of T
+ * lockstep steps of E envs from reset with the MLP agent net of mm_moffq_* (P: the trunk vector; the recurrent
+ * tensors are not read) and the epsilon-greedy draw of mm_offq_collect (same RNG, salts and per-(env, agent) streams,
+ * ctr = counter + t). An env that is done after its step is put back to the reset state before the next step, so all
+ * T * E transitions are valid. Transition j = t * E + e is written to slot (first + j) % size of every field's
+ * [size][row] store: obs / next_obs [N, D] (next_obs = the state after the step: the terminal observation at done, the
+ * reset observation is the next transition's obs), acts one-hot [N, A], rewards [N] (common_reward: the f32 agent-order
+ * sum for every agent, else each agent's own), dones [N] (Checkers: the env flag; Switch: the agent's own flag after
+ * the step), dones_env [1], valid_transition [N] (1; Switch: 1 - the agent's done flag before the step). first = 0,
+ * size = T * E gives plain [T * E, ...] staging tensors; an mm_mlpbuf's stores, cursor and capacity make the launch
+ * the insert (follow with mm_mlpbuf_advance). Requires T * E <= size, 0 <= first < size. Optional (may be NULL):
+ * q_out [T * E, N, A] indexed by j, ret_out [E] (agent 0's stored reward summed over the window), n_done_out int32 [E]
+ * (episodes finished in the window). The launch does not sync; eps and counter are read from device memory as in
+ * mm_offq_collect_io. Supported configurations and error reports: as mm_offq_collect / mm_offq_collect_switch. */
+typedef struct mm_moffq_collect_io {
+  const float* eps;
+  const uint64_t* counter;
+  uint64_t counter0, seed;
+  int32_t common_reward;
+  int64_t first, size;
+  float* obs; float* next_obs; float* acts; float* rewards; float* dones; float* dones_env; float* valid_transition;
+  float* q_out; float* ret_out; int32_t* n_done_out;
+} mm_moffq_collect_io;
+int mm_moffq_collect_supported(const mm_env* env, const mm_offq_dims* d, int64_t n_envs, int32_t T);
+int mm_moffq_collect(mm_env* env, const mm_offq_dims* d, const float* P, const mm_moffq_collect_io* io, int64_t n_envs,
+                     int32_t T, mm_stream_t s);
+int mm_moffq_collect_switch_supported(const mm_switch* env, const mm_offq_dims* d, int64_t n_envs, int32_t T);
+int mm_moffq_collect_switch(mm_switch* env, const mm_offq_dims* d, const float* P, const mm_moffq_collect_io* io,
+                            int64_t n_envs, int32_t T, mm_stream_t s);
+
+/* ------------------------------------------------------- offpolicy transition replay (mm_mlpbuf_*) */
+/* MlpReplayBuffer / PrioritizedMlpReplayBuffer of one policy (offpolicy/utils/mlp_buffer.py:10-340) in HBM: a ring of
+ * single transitions, each field a [size][row] store, with the f64 sum / min heaps, f32 alpha and max_priority of
+ * mm_erb_* (the same kernels). dones / dones_env start at 1, everything else at 0. The ring cursor and fill count
+ * are host state. store_share = 0 (needs S == N * D): share_obs / next_share_obs are not stored and a gather writes
+ * the transition's obs / next_obs row, which is the concatenation over agents. leaf_mode 0 = the reference's insert
+ * (mlp_buffer.py:282: range(idx_range[0], idx_range[1]), i.e. the first written slot's leaf, or none when the second
+ * written slot wrapped to 0); 1 = the leaf of every slot written. */
+typedef struct mm_mlpbuf mm_mlpbuf;
+typedef struct mm_mlpbuf_dims {
+  int32_t N, D, S, A;
+  int32_t store_share, prioritized, leaf_mode;
+} mm_mlpbuf_dims;
+/* Device pointers. insert: the reference's step-major arrays obs / next_obs [n, N, D], share_obs / next_share_obs
+ * [n, S], acts [n, N, A], rewards / dones / valid_transition [n, N, 1], dones_env [n, 1]. gather (sample_inds): the
+ * per-agent fields [N, B, X], share_obs / next_share_obs [B, S], dones_env [B, 1]; any may be NULL (not written).
+ * mm_mlpbuf_stores: the stores themselves (share pointers NULL without store_share). */
+typedef struct mm_mlpbuf_fields {
+  float* obs; float* share_obs; float* acts; float* rewards; float* next_obs; float* next_share_obs; float* dones;
+  float* dones_env; float* valid_transition;
+} mm_mlpbuf_fields;
+int mm_mlpbuf_create(const mm_mlpbuf_dims* d, int64_t buffer_size, double alpha, mm_mlpbuf** out);
+void mm_mlpbuf_destroy(mm_mlpbuf* b);
+/* MlpPolicyBuffer.insert + the prioritized leaf writes; 1 <= n <= size (leaf_mode 0 with prioritized: n >= 2, the
+ * reference reads idx_range[1]). idx_range_host (may be NULL): int64 [n], the ring slots written. */
+int mm_mlpbuf_insert(mm_mlpbuf* b, int32_t n, const mm_mlpbuf_fields* src, int64_t* idx_range_host, mm_stream_t s);
+int mm_mlpbuf_stores(mm_mlpbuf* b, mm_mlpbuf_fields* out);
+/* The bookkeeping of an insert whose n transitions something else (mm_moffq_collect*) has already written at the
+ * cursor: the leaf writes, then the cursor and fill count advance. */
+int mm_mlpbuf_advance(mm_mlpbuf* b, int64_t n, int64_t* idx_range_host, mm_stream_t s);
+int64_t mm_mlpbuf_len(const mm_mlpbuf* b);
+int64_t mm_mlpbuf_current(const mm_mlpbuf* b);   /* current_i: 0, then in (0, size] (size stands for slot 0) */
+int64_t mm_mlpbuf_it_capacity(const mm_mlpbuf* b);
+/* As mm_erb_sample_prioritized / mm_erb_sample_uniform / mm_erb_update_priorities / mm_erb_copy_state (the
+ * sum(0, len - 1) fold that leaves the last filled leaf out included). */
+int mm_mlpbuf_sample_prioritized(mm_mlpbuf* b, int32_t B, double beta, const double* fracs, uint64_t seed,
+                                 uint64_t counter, int64_t* idx_out, double* w_out, float* w32_out, mm_stream_t s);
+int mm_mlpbuf_sample_uniform(mm_mlpbuf* b, int32_t B, uint64_t seed, uint64_t counter, int64_t* idx_out, mm_stream_t s);
+/* sample_inds: one launch over all fields (an index outside [0, buffer_size) gathers zeros and sets bit 2 of the
+ * error word). */
+int mm_mlpbuf_gather(mm_mlpbuf* b, int32_t B, const int64_t* idx, const mm_mlpbuf_fields* dst, mm_stream_t s);
+int mm_mlpbuf_update_priorities(mm_mlpbuf* b, const int64_t* idx, const float* prio, int32_t B, mm_stream_t s);
+int mm_mlpbuf_copy_state(mm_mlpbuf* b, double* sum_dst, double* min_dst, float* maxp_dst, int32_t* err_dst,
+                         mm_stream_t s);
 
 /* Debug: copy the first n (<= 4096) u64 slots of the timing trace buffer that kernels fill when
  * MM_REC_TRACE=1 is set in the environment (clock64 stamps per phase; tools/trace_rec.py). mm_debug_trace(NULL, 0) allocates the buffer

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "erb_kernels.h"
 #include "minimarl.h"
 
 struct mm_erb {

@@ -6,12 +6,15 @@ GPU; the first op loads the library and raises if it was not built.
 """
 from ._lib import lib, symbols  # noqa: F401
 
-__all__ = ["lib", "symbols", "OffQCollector", "OffQRunner"]
+_LAZY = {"OffQCollector": "offq_runner", "OffQRunner": "offq_runner",
+         "MOffQCollector": "moffq_runner", "MOffQRunner": "moffq_runner",
+         "MlpReplayBuffer": "mlpbuf", "PrioritizedMlpReplayBuffer": "mlpbuf"}
+__all__ = ["lib", "symbols"] + list(_LAZY)
 
 
 def __getattr__(name):
-    # the offpolicy episode collector and runner (minimarl.offq_runner), imported on first use
-    if name in ("OffQCollector", "OffQRunner"):
-        from . import offq_runner
-        return getattr(offq_runner, name)
+    # the offpolicy collectors, runners and the transition replay, imported on first use
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

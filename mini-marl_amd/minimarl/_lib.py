@@ -441,6 +441,47 @@ _SIGS += [
 ]
 
 
+# ------------------------------------------------------------------ offpolicy transition collector and replay
+class MoffqCollectIO(ctypes.Structure):
+    """mm_moffq_collect_io (include/minimarl.h)"""
+    _fields_ = [("eps", c_vp), ("counter", c_vp), ("counter0", c_u64), ("seed", c_u64), ("common_reward", c_i32),
+                ("first", c_i64), ("size", c_i64),
+                ("obs", c_vp), ("next_obs", c_vp), ("acts", c_vp), ("rewards", c_vp), ("dones", c_vp),
+                ("dones_env", c_vp), ("valid_transition", c_vp), ("q_out", c_vp), ("ret_out", c_vp),
+                ("n_done_out", c_vp)]
+
+
+class MlpbufDims(ctypes.Structure):
+    _fields_ = [("N", c_i32), ("D", c_i32), ("S", c_i32), ("A", c_i32), ("store_share", c_i32),
+                ("prioritized", c_i32), ("leaf_mode", c_i32)]
+
+
+class MlpbufFields(ctypes.Structure):
+    _fields_ = [("obs", c_vp), ("share_obs", c_vp), ("acts", c_vp), ("rewards", c_vp), ("next_obs", c_vp),
+                ("next_share_obs", c_vp), ("dones", c_vp), ("dones_env", c_vp), ("valid_transition", c_vp)]
+
+
+_SIGS += [
+    ("mm_moffq_collect_supported", c_i32, [c_vp, _OD, c_i64, c_i32]),
+    ("mm_moffq_collect", c_i32, [c_vp, _OD, c_vp, ctypes.POINTER(MoffqCollectIO), c_i64, c_i32, c_vp]),
+    ("mm_moffq_collect_switch_supported", c_i32, [c_vp, _OD, c_i64, c_i32]),
+    ("mm_moffq_collect_switch", c_i32, [c_vp, _OD, c_vp, ctypes.POINTER(MoffqCollectIO), c_i64, c_i32, c_vp]),
+    ("mm_mlpbuf_create", c_i32, [ctypes.POINTER(MlpbufDims), c_i64, c_f64, ctypes.POINTER(c_vp)]),
+    ("mm_mlpbuf_destroy", None, [c_vp]),
+    ("mm_mlpbuf_insert", c_i32, [c_vp, c_i32, ctypes.POINTER(MlpbufFields), c_vp, c_vp]),
+    ("mm_mlpbuf_stores", c_i32, [c_vp, ctypes.POINTER(MlpbufFields)]),
+    ("mm_mlpbuf_advance", c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    ("mm_mlpbuf_len", c_i64, [c_vp]),
+    ("mm_mlpbuf_current", c_i64, [c_vp]),
+    ("mm_mlpbuf_it_capacity", c_i64, [c_vp]),
+    ("mm_mlpbuf_sample_prioritized", c_i32, [c_vp, c_i32, c_f64, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp]),
+    ("mm_mlpbuf_sample_uniform", c_i32, [c_vp, c_i32, c_u64, c_u64, c_vp, c_vp]),
+    ("mm_mlpbuf_gather", c_i32, [c_vp, c_i32, c_vp, ctypes.POINTER(MlpbufFields), c_vp]),
+    ("mm_mlpbuf_update_priorities", c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
+    ("mm_mlpbuf_copy_state", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+]
+
+
 # ------------------------------------------------------------------ ma_gym Switch env (mm_switch_*)
 class SwitchCfg(ctypes.Structure):
     _fields_ = [("n_agents", c_i32), ("max_steps", c_i32), ("full_observable", c_i32), ("clock", c_i32),

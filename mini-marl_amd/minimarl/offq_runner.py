@@ -113,30 +113,21 @@ class OffQRunner:
     ``total_env_steps`` by E per step (T E per collect), ``num_episodes_collected`` by E; ``total_train_steps`` by
     one per gradient update."""
 
+    ALGORITHMS = ("qmix", "vdn")
+
     def __init__(self, cfg=None, device="cuda", **overrides):
-        cfg = replace(cfg if cfg is not None else OffQTrainConfig(), **overrides)
-        assert cfg.algorithm_name in ("qmix", "vdn")
+        cfg = replace(cfg if cfg is not None else OffQTrainConfig(algorithm_name=self.ALGORITHMS[0]), **overrides)
+        assert cfg.algorithm_name in self.ALGORITHMS
         self.cfg = cfg
         self.device = torch.device(device)
         E, N, T = cfg.n_envs, cfg.n_agents, cfg.episode_length
         self.num_envs, self.num_agents, self.episode_length = E, N, T
         self.env = make_env(cfg.env, E, N, max_steps=T, step_cost=cfg.step_cost, full_observable=False, device=device)
         D, A = self.env.obs_dim, self.env.n_actions
-        self.trainer = OffQMix(N, D, A, T, cfg.batch_size, mixer=cfg.algorithm_name, hidden=cfg.hidden_size,
-                               mixer_hidden=cfg.mixer_hidden_dim, hyper_hidden=cfg.hypernet_hidden_dim,
-                               gamma=cfg.gamma, lr=cfg.lr, opti_eps=cfg.opti_eps, max_grad_norm=cfg.max_grad_norm,
-                               use_double_q=cfg.use_double_q, use_per=cfg.use_per, use_huber_loss=cfg.use_huber_loss,
-                               huber_delta=cfg.huber_delta, per_nu=cfg.per_nu, per_eps=cfg.per_eps, tau=cfg.tau,
-                               device=device, seed=cfg.seed)
-        self.collector = OffQCollector(self.env, self.trainer, T, cfg.seed, common_reward=cfg.use_common_reward)
+        self.trainer = self._make_trainer(D, A)
+        self.collector = self._make_collector()
         info = {"policy_0": {"obs_space": (D,), "share_obs_space": (N * D,), "act_space": (A,)}}
-        agents = {"policy_0": list(range(N))}
-        if cfg.use_per:
-            self.buffer = PrioritizedRecReplayBuffer(cfg.per_alpha, info, agents, cfg.buffer_size, T,
-                                                     cfg.use_same_share_obs, False, device=device, seed=cfg.seed)
-        else:
-            self.buffer = RecReplayBuffer(info, agents, cfg.buffer_size, T, cfg.use_same_share_obs, False,
-                                          device=device, seed=cfg.seed)
+        self.buffer = self._make_buffer(info, {"policy_0": list(range(N))})
         self.epsilon = DecayThenFlatSchedule(cfg.epsilon_start, cfg.epsilon_finish, cfg.epsilon_anneal_time)
         num_train_episodes = (cfg.num_env_steps / T) / cfg.train_interval_episode
         self.beta_anneal = DecayThenFlatSchedule(cfg.per_beta_start, 1.0, num_train_episodes)
@@ -147,6 +138,32 @@ class OffQRunner:
         self.last_hard_update_episode = 0
         self.train_infos = []
         self.env_info = {}
+
+    # -- what a runner of another algorithm family replaces: trainer, collector, buffer and the collect step
+    def _trainer_args(self):
+        """The configuration's keyword arguments that every offpolicy trainer takes."""
+        cfg = self.cfg
+        return dict(hidden=cfg.hidden_size, mixer_hidden=cfg.mixer_hidden_dim, hyper_hidden=cfg.hypernet_hidden_dim,
+                    gamma=cfg.gamma, lr=cfg.lr, opti_eps=cfg.opti_eps, max_grad_norm=cfg.max_grad_norm,
+                    use_double_q=cfg.use_double_q, use_per=cfg.use_per, use_huber_loss=cfg.use_huber_loss,
+                    huber_delta=cfg.huber_delta, per_eps=cfg.per_eps, tau=cfg.tau, device=self.device, seed=cfg.seed)
+
+    def _make_trainer(self, D, A):
+        cfg = self.cfg
+        return OffQMix(self.num_agents, D, A, self.episode_length, cfg.batch_size, mixer=cfg.algorithm_name,
+                       per_nu=cfg.per_nu, **self._trainer_args())
+
+    def _make_collector(self):
+        return OffQCollector(self.env, self.trainer, self.episode_length, self.cfg.seed,
+                             common_reward=self.cfg.use_common_reward)
+
+    def _make_buffer(self, info, agents):
+        cfg, T = self.cfg, self.episode_length
+        if cfg.use_per:
+            return PrioritizedRecReplayBuffer(cfg.per_alpha, info, agents, cfg.buffer_size, T, cfg.use_same_share_obs,
+                                              False, device=self.device, seed=cfg.seed)
+        return RecReplayBuffer(info, agents, cfg.buffer_size, T, cfg.use_same_share_obs, False, device=self.device,
+                               seed=cfg.seed)
 
     def _collect(self, eps):
         fields, returns, _ = self.collector.collect(eps)
