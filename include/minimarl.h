@@ -1047,6 +1047,56 @@ int mm_mlpbuf_update_priorities(mm_mlpbuf* b, const int64_t* idx, const float* p
 int mm_mlpbuf_copy_state(mm_mlpbuf* b, double* sum_dst, double* min_dst, float* maxp_dst, int32_t* err_dst,
                          mm_stream_t s);
 
+/* ------------------------------------------------------------------ offpolicy feed-forward MADDPG / MATD3 ("maddpg" / "matd3")
+ * Replaces MADDPG.shared_train_policy_on_batch (offpolicy/algorithms/maddpg/maddpg.py:90-249) with MADDPGPolicy
+ * (algorithm/MADDPGPolicy.py:63-151) for discrete actions and one shared policy (csrc/maddpg.hip).
+ * actor: the feed-forward agent net of mm_moffq_* in the trunk layout with D = obs_dim (A logits in the Wo / bo slot).
+ * critic: the same trunk over [cent_obs | cent_act], width Dc = N (D + A) <= MM_MADDPG_MAX_CRITIC_WIDTH, W1 rows padded
+ * to ceil4(Dc), with 1 (maddpg) or 2 (td3) 64 -> 1 heads in the 4-row Wo / bo slot, which is LAST in the vector
+ * (mm_maddpg_param_counts: critic_heads = its offset). The heads are not parameters in the reference
+ * (actor_critic.py:67, a plain list): their gradient is exactly zero, and the caller keeps the slot out of target
+ * updates. The recurrent tensors of both layouts are not read and get zero gradient.
+ * Batch = MlpReplayBuffer.sample layout: obs / nobs [N, B, D], cent_obs / cent_nobs [B, N D], acts one-hot [N, B, A],
+ * rewards [N, B] (agent 0's are used), dones_env [B], valid [N, B] (valid_transition; actor pass), is_weight [B]
+ * (NULL: no PER), gumbel / target_gumbel [N, B, A]: Gumbel(0, 1) noise of the actor pass / of matd3's target actions
+ * (mm_maddpg_gumbel fills one from the counter RNG).
+ * One update = mm_maddpg_critic_grad, mm_clip_adam on the critic, mm_maddpg_actor_grad (reads the UPDATED critic),
+ * mm_clip_adam on the actor. Each grad call is two launches (fused tile kernel + fixed-order reduction); same inputs
+ * give the same bits. Supported: H = 64, A = 5, D in {3, 47, 94}, N >= 1, B >= 1; anything else MM_EINVAL (-1 from the
+ * size query) before any launch. */
+#define MM_MADDPG_MAX_CRITIC_WIDTH 416
+typedef struct mm_maddpg_dims {
+  int32_t n_agents, obs_dim, hidden, n_actions;
+  int32_t td3;                                     /* 0: maddpg (one head), 1: matd3 (two heads, Gumbel target actions) */
+} mm_maddpg_dims;
+typedef struct mm_maddpg_batch {
+  const float* obs; const float* nobs; const float* cent_obs; const float* cent_nobs; const float* acts;
+  const float* rewards; const float* dones_env; const float* valid; const float* is_weight;
+  const float* gumbel; const float* target_gumbel;
+  int32_t B, huber;
+  float gamma, huber_delta, per_eps;
+} mm_maddpg_batch;
+int mm_maddpg_param_counts(const mm_maddpg_dims* d, int64_t* actor, int64_t* critic, int64_t* critic_heads);
+int64_t mm_maddpg_workspace_bytes(const mm_maddpg_dims* d, int32_t B);
+/* Critic pass: target = r + gamma (1 - done_env) min_h Q'_h(cent_nobs, target-actor actions), err_h = target - Q_h,
+ * loss = sum_h mean_b w_b f(err_h) (f = e^2 or Huber), priorities mean_h |err_h| + per_eps (PER only). grad: the
+ * critic layout; stats float[2] = {loss, 0}. ws: mm_maddpg_workspace_bytes(d, B), needs no initialisation. */
+int mm_maddpg_critic_grad(const mm_maddpg_dims* d, const mm_maddpg_batch* b, const float* PA_target, const float* PC,
+                          const float* PC_target, float* grad, void* ws, int64_t ws_bytes, float* stats,
+                          float* priorities, mm_stream_t s);
+/* Actor pass: y = softmax(logits + gumbel), hard = one-hot argmax; for each agent i the stored cent_act with only
+ * agent i's columns replaced by hard_i goes through critic head 0; loss = -sum Q_i valid_i / sum valid; the gradient
+ * reaches the actor straight through (d hard := d y). grad: the actor layout; stats float[2] = {loss, sum valid}. */
+int mm_maddpg_actor_grad(const mm_maddpg_dims* d, const mm_maddpg_batch* b, const float* PA, const float* PC,
+                         float* grad, void* ws, int64_t ws_bytes, float* stats, mm_stream_t s);
+/* Actor logits [R, A] of obs [R, D]. onehot (may be NULL) [R, A]: with gumbel [R, A] the one-hot argmax of
+ * logits + gumbel, without it logits == rowmax (onehot_from_logits: multi-hot on an exact tie). */
+int mm_maddpg_logits(const mm_maddpg_dims* d, const float* PA, const float* obs, const float* gumbel, float* logits,
+                     float* onehot, int64_t R, mm_stream_t s);
+/* g [N, B, A] = -log(-log(U + 1e-20) + 1e-20), U = rng_uniform(rng_draw(seed, counter, b, n A + a)); f32 values, each
+ * log evaluated in f64 and rounded. */
+int mm_maddpg_gumbel(const mm_maddpg_dims* d, float* g, int32_t B, uint64_t seed, uint64_t counter, mm_stream_t s);
+
 /* Debug: copy the first n (<= 4096) u64 slots of the timing trace buffer that kernels fill when
  * MM_REC_TRACE=1 is set in the environment (clock64 stamps per phase; tools/trace_rec.py). mm_debug_trace(NULL, 0) allocates the buffer
  * (call it before any graph capture). */

@@ -41,187 +41,21 @@
 
 #include "common.h"
 #include "minimarl.h"
-#include "trunk.h"
+#include "mq_tile.h"
 
 namespace mm {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int MQ_TB = 16;           // transitions per tile = rows of one MFMA tile
 constexpr int MQ_MAX_BLOCKS = 256;  // one block per CU; also bounds the partials
 constexpr int MQ_Q_BLOCKS = 256;
 
-// v_mfma_f32_16x16x4_f32: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
-// D reg r of lane (j, g = lane >> 4): row 4 g + r, column j
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// C(i, n) = sum_k X[i ldx + k] W[n ldn + k ldk] for i < rows (<= 16), n < ncols; epi(i, n, C). One 16-column tile
-// per wave and pass. X and W may be LDS or global. relu_x: max(X, 0) on load.
-template <typename Epi>
-__device__ __forceinline__ void mq_gemm(const float* X, int64_t ldx, bool relu_x, int rows, const float* W,
-                                        int64_t ldn, int64_t ldk, int ncols, int kdim, Epi epi) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const bool rok = j < rows;
-  const float* xp = X + j * ldx;
-  for (int n0 = wave * 16; n0 < ncols; n0 += 64) {
-    const bool nok = n0 + j < ncols;
-    const float* wp = W + (n0 + j) * ldn;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < kdim; k0 += 4) {
-      const int k = k0 + g;
-      float av = (rok && k < kdim) ? xp[k] : 0.f;
-      if (relu_x) av = fmaxf(av, 0.f);
-      const float bv = (nok && k < kdim) ? wp[k * ldk] : 0.f;
-      acc = mfma16(av, bv, acc);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (4 * g + r < rows && nok) epi(4 * g + r, n0 + j, acc[r]);
-  }
-}
-
-// out[m ldo + k] += sum_{r < rows} dY[r ldy + m] X[r ldx + k] for m < M, k < Kc: the tile's rows on the MFMA k
-// dimension. An output element always belongs to the same lane of the same wave, which adds into the block-private
-// partial in tile order.
-__device__ __forceinline__ void mq_wgrad(const float* dY, int64_t ldy, const float* X, int64_t ldx, bool relu_x,
-                                         int rows, int M, int Kc, float* out, int64_t ldo) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-  const int MT = (M + 15) >> 4, KT = (Kc + 15) >> 4;
-  for (int t = wave; t < MT * KT; t += 4) {
-    const int m0 = (t / KT) * 16, k0 = (t % KT) * 16;
-    const bool mok = m0 + j < M, kok = k0 + j < Kc;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r0 = 0; r0 < MQ_TB; r0 += 4) {
-      const int r = r0 + g;
-      const float av = (r < rows && mok) ? dY[r * ldy + m0 + j] : 0.f;
-      float bv = (r < rows && kok) ? X[r * ldx + k0 + j] : 0.f;
-      if (relu_x) bv = fmaxf(bv, 0.f);
-      acc = mfma16(av, bv, acc);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + 4 * g + r;
-      if (m < M && kok) out[m * ldo + k0 + j] += acc[r];
-    }
-  }
-}
-
-// out[m] += sum_{r < rows} dY[r ldy + m] (* X[r ldx + m]) in row order
-__device__ __forceinline__ void mq_colsum(const float* dY, int64_t ldy, const float* X, int64_t ldx, int rows, int M,
-                                          float* out) {
-  for (int m = threadIdx.x; m < M; m += blockDim.x) {
-    float s = 0.f;
-    for (int r = 0; r < rows; ++r) s += X ? dY[r * ldy + m] * X[r * ldx + m] : dY[r * ldy + m];
-    out[m] += s;
-  }
-}
-
-__device__ __forceinline__ float sum16(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
-
-// LayerNorm of 16 rows, 16 lanes per row: Y = xhat gw + gb, XH = xhat, rs[row]
-__device__ __forceinline__ void mq_ln(const float* X, int64_t ldx, int rows, int ncols, const float* gw,
-                                      const float* gb, float* Y, float* XH, int ld, float* rs_out) {
-  const int row = threadIdx.x >> 4, sub = threadIdx.x & 15;
-  const bool ok = row < rows;
-  const float* xp = X + row * ldx;
-  float s = 0.f;
-  for (int c = sub; c < ncols; c += 16) s += ok ? xp[c] : 0.f;
-  const float mu = sum16(s) / (float)ncols;
-  float v = 0.f;
-  for (int c = sub; c < ncols; c += 16) {
-    const float d = ok ? xp[c] - mu : 0.f;
-    v = fmaf(d, d, v);
-  }
-  const float rs = 1.0f / sqrtf(sum16(v) / (float)ncols + kLnEps);
-  if (!ok) return;
-  for (int c = sub; c < ncols; c += 16) {
-    const float xh = (xp[c] - mu) * rs;
-    XH[row * ld + c] = xh;
-    Y[row * ld + c] = xh * gw[c] + gb[c];
-  }
-  if (sub == 0) rs_out[row] = rs;
-}
-
-// In place: G = dL/dy of a LayerNorm over 64 columns -> dL/d(pre-activation of the ReLU in front of it):
-// rs (g - mean g - xhat mean(g xhat)), g = dy gw, zero where the ReLU output Aact is 0
-__device__ __forceinline__ void mq_ln_bwd(float* G, const float* XH, const float* Aact, const float* rs,
-                                          const float* gw, int rows, int ld) {
-  const int row = threadIdx.x >> 4, sub = threadIdx.x & 15;
-  const bool ok = row < rows;
-  float sg = 0.f, sgx = 0.f;
-  for (int c = sub; c < 64; c += 16) {
-    const float gg = ok ? G[row * ld + c] * gw[c] : 0.f;
-    sg += gg;
-    sgx = fmaf(gg, ok ? XH[row * ld + c] : 0.f, sgx);
-  }
-  sg = sum16(sg) * (1.0f / 64);
-  sgx = sum16(sgx) * (1.0f / 64);
-  if (!ok) return;
-  for (int c = sub; c < 64; c += 16) {
-    const float dx = rs[row] * (G[row * ld + c] * gw[c] - sg - XH[row * ld + c] * sgx);
-    G[row * ld + c] = Aact[row * ld + c] > 0.0f ? dx : 0.0f;
-  }
-}
-
-// LDS carve-up (floats). Row strides are odd: 16 rows of one column fall into 16 different banks.
-template <int D>
-struct MqL {
-  static constexpr int Dp = (D + 3) & ~3, ld0 = Dp + 1, ldh = 65;
-  static constexpr int wW1 = 0, wW2 = wW1 + 64 * ld0, wWo = wW2 + 64 * ldh, nW = wWo + 8 * ldh;  // one net's weights
-  static constexpr int F0 = 0, XH0 = F0 + MQ_TB * ld0, G0 = XH0 + MQ_TB * ld0;
-  static constexpr int A1 = G0 + MQ_TB * ld0, XH1 = A1 + MQ_TB * ldh, F1 = XH1 + MQ_TB * ldh;
-  static constexpr int A2 = F1 + MQ_TB * ldh, XH2 = A2 + MQ_TB * ldh, F2 = XH2 + MQ_TB * ldh;
-  static constexpr int G1 = F2 + MQ_TB * ldh, G2 = G1 + MQ_TB * ldh;
-  static constexpr int Q = G2 + MQ_TB * ldh, DO = Q + MQ_TB * 8, RS = DO + MQ_TB * 8;   // RS: rs0, rs1, rs2 [16] each
-  static constexpr int DQ = RS + 3 * MQ_TB, LS = DQ + MQ_TB, QT = LS + MQ_TB, ARG = QT + 2 * MQ_TB;
-  static constexpr int nAct = ARG + MQ_TB;
-  static constexpr int train_bytes = (2 * nW + nAct) * 4, q_bytes = (nW + nAct) * 4;
-};
-
-template <int D, int H, int A>
-__device__ __forceinline__ void mq_stage(float* w, const float* __restrict__ P) {
-  using G = MGeo<D, H, A>;
-  using L = MqL<D>;
-  for (int e = threadIdx.x; e < 64 * G::Dp; e += blockDim.x)
-    w[L::wW1 + (e / G::Dp) * L::ld0 + e % G::Dp] = P[G::W1 + e];
-  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) w[L::wW2 + (e >> 6) * L::ldh + (e & 63)] = P[G::W2 + e];
-  for (int e = threadIdx.x; e < G::Op * 64; e += blockDim.x) w[L::wWo + (e >> 6) * L::ldh + (e & 63)] = P[G::Wo + e];
-}
-
 // Forward of one net over a 16-row chunk x (row stride D, global): leaves F0 XH0 A1 XH1 F1 A2 XH2 F2 RS and
-// Q [16][8] in LDS. Ends with a barrier.
+// Q [16][8] in LDS (mq_tile.h; weights staged by mq_stage). Ends with a barrier.
 template <int D, int H, int A>
 __device__ __forceinline__ void mq_agent_fwd(const float* __restrict__ P, const float* w, const float* x, int rows,
                                              float* act) {
   static_assert(H == 64, "64 hidden units: one 16-column MFMA tile per wave");
-  using G = MGeo<D, H, A>;
-  using L = MqL<D>;
-  mq_ln(x, D, rows, D, P + G::ln0_w, P + G::ln0_b, act + L::F0, act + L::XH0, L::ld0, act + L::RS);
-  __syncthreads();
-  mq_gemm(act + L::F0, L::ld0, false, rows, w + L::wW1, L::ld0, 1, H, D,
-          [&](int i, int n, float v) { act[L::A1 + i * L::ldh + n] = fmaxf(v + P[G::b1 + n], 0.0f); });
-  __syncthreads();
-  mq_ln(act + L::A1, L::ldh, rows, H, P + G::ln1_w, P + G::ln1_b, act + L::F1, act + L::XH1, L::ldh,
-        act + L::RS + MQ_TB);
-  __syncthreads();
-  mq_gemm(act + L::F1, L::ldh, false, rows, w + L::wW2, L::ldh, 1, H, H,
-          [&](int i, int n, float v) { act[L::A2 + i * L::ldh + n] = fmaxf(v + P[G::b2 + n], 0.0f); });
-  __syncthreads();
-  mq_ln(act + L::A2, L::ldh, rows, H, P + G::ln2_w, P + G::ln2_b, act + L::F2, act + L::XH2, L::ldh,
-        act + L::RS + 2 * MQ_TB);
-  __syncthreads();
-  mq_gemm(act + L::F2, L::ldh, false, rows, w + L::wWo, L::ldh, 1, A, H,
-          [&](int i, int n, float v) { act[L::Q + i * 8 + n] = v + P[G::bo + n]; });
-  __syncthreads();
+  mq_mlp_fwd(MGeo<D, H, A>{}, MqL<D>{}, MqL<D>{}, P, w, x, D, D, A, rows, act);
 }
 
 // per-block scratch slice (float offsets): per-agent Q and the mixer's tile intermediates
@@ -488,43 +322,12 @@ __global__ __launch_bounds__(256) void moffq_train_kernel(MqArgs a) {
     for (int n = 0; n < N; ++n) {
       const int64_t r0 = (int64_t)n * a.B + b0;
       mq_agent_fwd<D, H, A>(a.P, wb, a.obs + r0 * D, rows, act);
-      float* dO = act + L::DO;
-      float* G2 = act + L::G2;
-      float* G1 = act + L::G1;
-      float* G0 = act + L::G0;
       if (tid < MQ_TB * 8) {
         const int i = tid >> 3, k = tid & 7;
-        dO[tid] = (i < rows && k == aidx[n * MQ_TB + i]) ? dqa[n * MQ_TB + i] : 0.0f;
+        act[L::DO + tid] = (i < rows && k == aidx[n * MQ_TB + i]) ? dqa[n * MQ_TB + i] : 0.0f;
       }
       __syncthreads();
-      mq_wgrad(dO, 8, act + L::F2, L::ldh, false, rows, A, H, part + G::Wo, H);
-      mq_colsum(dO, 8, nullptr, 0, rows, A, part + G::bo);
-      mq_gemm(dO, 8, false, rows, wb + L::wWo, 1, L::ldh, H, A,
-              [&](int i, int k, float v) { G2[i * L::ldh + k] = v; });
-      __syncthreads();
-      mq_colsum(G2, L::ldh, act + L::XH2, L::ldh, rows, H, part + G::ln2_w);
-      mq_colsum(G2, L::ldh, nullptr, 0, rows, H, part + G::ln2_b);
-      __syncthreads();
-      mq_ln_bwd(G2, act + L::XH2, act + L::A2, act + L::RS + 2 * MQ_TB, a.P + G::ln2_w, rows, L::ldh);
-      __syncthreads();
-      mq_wgrad(G2, L::ldh, act + L::F1, L::ldh, false, rows, H, H, part + G::W2, H);
-      mq_colsum(G2, L::ldh, nullptr, 0, rows, H, part + G::b2);
-      mq_gemm(G2, L::ldh, false, rows, wb + L::wW2, 1, L::ldh, H, H,
-              [&](int i, int k, float v) { G1[i * L::ldh + k] = v; });
-      __syncthreads();
-      mq_colsum(G1, L::ldh, act + L::XH1, L::ldh, rows, H, part + G::ln1_w);
-      mq_colsum(G1, L::ldh, nullptr, 0, rows, H, part + G::ln1_b);
-      __syncthreads();
-      mq_ln_bwd(G1, act + L::XH1, act + L::A1, act + L::RS + MQ_TB, a.P + G::ln1_w, rows, L::ldh);
-      __syncthreads();
-      mq_wgrad(G1, L::ldh, act + L::F0, L::ld0, false, rows, H, D, part + G::W1, G::Dp);
-      mq_colsum(G1, L::ldh, nullptr, 0, rows, H, part + G::b1);
-      mq_gemm(G1, L::ldh, false, rows, wb + L::wW1, 1, L::ld0, D, H,
-              [&](int i, int k, float v) { G0[i * L::ld0 + k] = v; });
-      __syncthreads();
-      mq_colsum(G0, L::ld0, act + L::XH0, L::ld0, rows, D, part + G::ln0_w);
-      mq_colsum(G0, L::ld0, nullptr, 0, rows, D, part + G::ln0_b);
-      __syncthreads();
+      mq_mlp_bwd(G{}, L{}, L{}, a.P, wb, D, A, rows, true, true, act, part);
     }
   }
   if (tid == 0) {

@@ -502,3 +502,29 @@ _SIGS += [
     ("mm_switch_step_rows_td", c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 ]
+
+
+# ------------------------------------------------------------------ offpolicy MADDPG / MATD3 (mm_maddpg_*)
+class MaddpgDims(ctypes.Structure):
+    """mm_maddpg_dims (include/minimarl.h)"""
+    _fields_ = [("n_agents", c_i32), ("obs_dim", c_i32), ("hidden", c_i32), ("n_actions", c_i32), ("td3", c_i32)]
+
+
+class MaddpgBatch(ctypes.Structure):
+    """mm_maddpg_batch (include/minimarl.h)"""
+    _fields_ = [("obs", c_vp), ("nobs", c_vp), ("cent_obs", c_vp), ("cent_nobs", c_vp), ("acts", c_vp),
+                ("rewards", c_vp), ("dones_env", c_vp), ("valid", c_vp), ("is_weight", c_vp), ("gumbel", c_vp),
+                ("target_gumbel", c_vp), ("B", c_i32), ("huber", c_i32), ("gamma", c_f32), ("huber_delta", c_f32),
+                ("per_eps", c_f32)]
+
+
+_MD = ctypes.POINTER(MaddpgDims)
+_SIGS += [
+    ("mm_maddpg_param_counts", c_i32, [_MD, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    ("mm_maddpg_workspace_bytes", c_i64, [_MD, c_i32]),
+    ("mm_maddpg_critic_grad", c_i32, [_MD, ctypes.POINTER(MaddpgBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                      c_vp, c_vp]),
+    ("mm_maddpg_actor_grad", c_i32, [_MD, ctypes.POINTER(MaddpgBatch), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    ("mm_maddpg_logits", c_i32, [_MD, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    ("mm_maddpg_gumbel", c_i32, [_MD, c_vp, c_i32, c_u64, c_u64, c_vp]),
+]
