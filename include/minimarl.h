@@ -26,6 +26,8 @@
  *   mm_moffq_*           offpolicy M_QMix.train_policy_on_batch (feed-forward, transition batches)  offpolicy/algorithms/mqmix/mqmix.py:68-218
  *   mm_erb_*             PrioritizedRecReplayBuffer / RecReplayBuffer offpolicy/utils/rec_buffer.py:10-324; segment_tree.py:18-165
  *   mm_moffq_collect*    the MLP runner's collect loop for mqmix / mvdn: a window of transitions in one launch
+ *   mm_maddpg_*          offpolicy MADDPG / MATD3 shared_train_policy_on_batch  offpolicy/algorithms/maddpg/maddpg.py:90-249
+ *   (minimarl_maddpg_collect.h: the MLP runner's collect loop for maddpg / matd3, Gumbel-softmax exploration of the actor)
  *   mm_mlpbuf_*          PrioritizedMlpReplayBuffer / MlpReplayBuffer offpolicy/utils/mlp_buffer.py:10-340
  *   mm_eval_accum        greedy test loops                           vdn/_test.py:22-50; magym_runner.py:198-241
  */
@@ -1105,4 +1107,6 @@ int mm_debug_trace(uint64_t* host_out, int32_t n);
 #ifdef __cplusplus
 }
 #endif
+/* the transition collector of maddpg / matd3 (mm_maddpg_collect*) is declared in a header of its own */
+#include "minimarl_maddpg_collect.h"
 #endif

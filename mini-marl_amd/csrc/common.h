@@ -76,6 +76,13 @@ __device__ __forceinline__ float rollout_td(float sr, float sq, float st, float 
   return fabsf(__fsub_rn(__fadd_rn(sr, boot), sq));
 }
 __device__ __forceinline__ float rng_uniform(uint64_t r) { return (float)(r >> 40) * (1.0f / 16777216.0f); }
+// Gumbel(0, 1) draw -log(-log(U + 1e-20) + 1e-20) of U = rng_uniform(r): sums and result f32, each log evaluated in f64
+// and rounded, so a host twin reproduces the bits
+__device__ __forceinline__ float rng_gumbel(uint64_t r) {
+  const float u = rng_uniform(r) + 1e-20f;
+  const float t = -(float)log((double)u) + 1e-20f;
+  return -(float)log((double)t);
+}
 // r % m for 1 <= m <= 65536 in 32-bit arithmetic (exact: r = hi 2^32 + lo, (hi % m)(2^32 % m) + lo % m < 2^32)
 __device__ __forceinline__ uint32_t rng_mod_small(uint64_t r, uint32_t m) {
   const uint32_t p32 = (0xFFFFFFFFu % m + 1u) % m;   // 2^32 mod m

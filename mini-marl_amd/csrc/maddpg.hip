@@ -415,9 +415,7 @@ __global__ void md_gumbel_kernel(float* g, int N, int B, uint64_t seed, uint64_t
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (e >= (int64_t)N * B * MD_A) return;
   const int k = (int)(e % MD_A), b = (int)(e / MD_A % B), n = (int)(e / ((int64_t)MD_A * B));
-  const float u = rng_uniform(rng_draw(seed, counter, (uint64_t)b, (uint64_t)(n * MD_A + k))) + 1e-20f;
-  const float t = -(float)log((double)u) + 1e-20f;
-  g[e] = -(float)log((double)t);
+  g[e] = rng_gumbel(rng_draw(seed, counter, (uint64_t)b, (uint64_t)(n * MD_A + k)));
 }
 
 int md_blocks(int B) { return std::min((B + MQ_TB - 1) / MQ_TB, MD_MAX_BLOCKS); }

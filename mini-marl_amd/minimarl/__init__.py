@@ -8,7 +8,8 @@ from ._lib import lib, symbols  # noqa: F401
 
 _LAZY = {"OffQCollector": "offq_runner", "OffQRunner": "offq_runner",
          "MOffQCollector": "moffq_runner", "MOffQRunner": "moffq_runner",
-         "MlpReplayBuffer": "mlpbuf", "PrioritizedMlpReplayBuffer": "mlpbuf", "MADDPG": "maddpg"}
+         "MlpReplayBuffer": "mlpbuf", "PrioritizedMlpReplayBuffer": "mlpbuf", "MADDPG": "maddpg",
+         "MADDPGCollector": "maddpg_runner", "MADDPGRunner": "maddpg_runner"}
 __all__ = ["lib", "symbols"] + list(_LAZY)
 
 

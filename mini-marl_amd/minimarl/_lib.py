@@ -528,3 +528,16 @@ _SIGS += [
     ("mm_maddpg_logits", c_i32, [_MD, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     ("mm_maddpg_gumbel", c_i32, [_MD, c_vp, c_i32, c_u64, c_u64, c_vp]),
 ]
+
+
+class MaddpgCollectIO(MoffqCollectIO):
+    """mm_maddpg_collect_io (include/minimarl_maddpg_collect.h): the members of mm_moffq_collect_io (``w``), then these"""
+    _fields_ = [("gumbel_seed", c_u64), ("explore", c_i32)]
+
+
+_SIGS += [
+    ("mm_maddpg_collect_supported", c_i32, [c_vp, _MD, c_i64, c_i32]),
+    ("mm_maddpg_collect", c_i32, [c_vp, _MD, c_vp, ctypes.POINTER(MaddpgCollectIO), c_i64, c_i32, c_vp]),
+    ("mm_maddpg_collect_switch_supported", c_i32, [c_vp, _MD, c_i64, c_i32]),
+    ("mm_maddpg_collect_switch", c_i32, [c_vp, _MD, c_vp, ctypes.POINTER(MaddpgCollectIO), c_i64, c_i32, c_vp]),
+]

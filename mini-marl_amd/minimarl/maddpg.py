@@ -35,6 +35,7 @@ from .qnet import ptr, stream_handle
 
 MAX_CRITIC_WIDTH = 416          # MM_MADDPG_MAX_CRITIC_WIDTH (include/minimarl.h)
 GUMBEL_SALT, TARGET_GUMBEL_SALT, ACT_GUMBEL_SALT = 0x67756D62656C0001, 0x67756D62656C0002, 0x67756D62656C0003
+COLLECT_GUMBEL_SALT = 0x67756D62656C0004       # the device collector's exploration noise (minimarl.maddpg_runner)
 TRUNK_REF = {
     "ln0_w": "mlp.feature_norm.weight", "ln0_b": "mlp.feature_norm.bias",
     "W1": "mlp.mlp.fc1.0.weight", "b1": "mlp.mlp.fc1.0.bias",

@@ -40,6 +40,10 @@ class MOffQCollector:
     neither read nor written. The launch does not sync and reads epsilon and the RNG step counter from device memory,
     so a captured ``launch()`` replays with whatever ``set_epsilon`` / ``counter`` hold at replay time."""
 
+    # what a collector of another algorithm family replaces: the entry points (Checkers, Switch), their io struct and
+    # the policy's parameter vector the launch reads
+    _names, _io_type, _params = ("moffq_collect", "moffq_collect_switch"), MoffqCollectIO, "P"
+
     def __init__(self, env, policy, T, seed, common_reward=True, with_q=False):
         self.env, self.policy = env, policy
         self.E, self.N, self.T = int(env.E), int(env.N), int(T)
@@ -47,11 +51,8 @@ class MOffQCollector:
         self.device = policy.device
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.common_reward = bool(common_reward)
-        if isinstance(env, SwitchVecEnv):
-            self._name, supported = "moffq_collect_switch", lib().mm_moffq_collect_switch_supported
-        else:
-            self._name, supported = "moffq_collect", lib().mm_moffq_collect_supported
-        self._collect = getattr(lib(), "mm_" + self._name)
+        self._name = self._names[isinstance(env, SwitchVecEnv)]
+        self._collect, supported = getattr(lib(), "mm_" + self._name), getattr(lib(), "mm_" + self._name + "_supported")
         if not supported(env.handle(), ctypes.byref(policy.dims), self.E, self.T):
             # the launch reports why
             check(self._collect(env.handle(), ctypes.byref(policy.dims), None, None, self.E, self.T, None), self._name)
@@ -68,7 +69,7 @@ class MOffQCollector:
         self._io = self._make_io({k: ptr(v) for k, v in self.fields.items()}, 0, n)
 
     def _make_io(self, p, first, size):
-        io = MoffqCollectIO()
+        io = self._io_type()
         io.eps, io.counter, io.counter0, io.seed = ptr(self.eps), ptr(self.counter), 0, self.seed
         io.common_reward = int(self.common_reward)
         io.first, io.size = int(first), int(size)
@@ -86,8 +87,8 @@ class MOffQCollector:
         (an ``MlpbufFields`` of [size][row] device stores) the window goes to ring slots (first + j) % size of them
         instead of the staging tensors."""
         io = self._io if stores is None else self._make_io({k: getattr(stores, k) for k in STAGED}, first, size)
-        check(self._collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(self.policy.P), ctypes.byref(io),
-                            self.E, self.T, stream_handle(self.device)), self._name)
+        check(self._collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(getattr(self.policy, self._params)),
+                            ctypes.byref(io), self.E, self.T, stream_handle(self.device)), self._name)
         self.counter.add_(self.T)
 
     def collect(self, eps):
