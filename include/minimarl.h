@@ -1109,4 +1109,6 @@ int mm_debug_trace(uint64_t* host_out, int32_t n);
 #endif
 /* the transition collector of maddpg / matd3 (mm_maddpg_collect*) is declared in a header of its own */
 #include "minimarl_maddpg_collect.h"
+/* the recurrent trainer rmaddpg / rmatd3 (mm_rmaddpg_*) likewise */
+#include "minimarl_rmaddpg.h"
 #endif

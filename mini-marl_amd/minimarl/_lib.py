@@ -541,3 +541,22 @@ _SIGS += [
     ("mm_maddpg_collect_switch_supported", c_i32, [c_vp, _MD, c_i64, c_i32]),
     ("mm_maddpg_collect_switch", c_i32, [c_vp, _MD, c_vp, ctypes.POINTER(MaddpgCollectIO), c_i64, c_i32, c_vp]),
 ]
+
+
+# ------------------------------------------------------------------ offpolicy recurrent MADDPG / MATD3 (mm_rmaddpg_*)
+class RmaddpgBatch(ctypes.Structure):
+    """mm_rmaddpg_batch (include/minimarl_rmaddpg.h)"""
+    _fields_ = [("obs", c_vp), ("share_obs", c_vp), ("acts", c_vp), ("rewards", c_vp), ("dones", c_vp),
+                ("dones_env", c_vp), ("is_weight", c_vp), ("gumbel", c_vp), ("target_gumbel", c_vp), ("T", c_i32),
+                ("B", c_i32), ("huber", c_i32), ("gamma", c_f32), ("huber_delta", c_f32), ("per_eps", c_f32),
+                ("per_nu", c_f32)]
+
+
+_SIGS += [
+    ("mm_rmaddpg_param_counts", c_i32, [_MD, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    ("mm_rmaddpg_workspace_bytes", c_i64, [_MD, c_i32, c_i32]),
+    ("mm_rmaddpg_critic_grad", c_i32, [_MD, ctypes.POINTER(RmaddpgBatch), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                       c_vp, c_vp]),
+    ("mm_rmaddpg_actor_grad", c_i32, [_MD, ctypes.POINTER(RmaddpgBatch), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    ("mm_rmaddpg_step", c_i32, [_MD, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+]

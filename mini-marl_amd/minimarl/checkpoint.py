@@ -11,6 +11,8 @@ Supported components (``checkpoint_tensors()`` / ``restore_tensors()`` protocol)
   OffQMix       behavior + target [agent | mixer], Adam m / v / step
   MADDPG        actor and critic parameters (critic heads included), their targets, both Adam states; scalars: td3,
                 the update counter and the noise-call counter
+  RMADDPG       the same tensors for the recurrent trainer (save_checkpoint(path, rmaddpg=tr)); scalars: td3, the
+                update counter and the noise-call counter
   MappoTrainer  actor / critic parameters, both Adam states, ValueNorm running statistics; scalar: the number of
                 train() calls (seeds the minibatch permutations; 0 when absent) and the policy mode (recurrent 1 | 0;
                 recurrent when absent; loading across modes raises ValueError)
