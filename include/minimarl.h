@@ -28,6 +28,7 @@
  *   mm_moffq_collect*    the MLP runner's collect loop for mqmix / mvdn: a window of transitions in one launch
  *   mm_maddpg_*          offpolicy MADDPG / MATD3 shared_train_policy_on_batch  offpolicy/algorithms/maddpg/maddpg.py:90-249
  *   (minimarl_maddpg_collect.h: the MLP runner's collect loop for maddpg / matd3, Gumbel-softmax exploration of the actor)
+ *   (minimarl_rmaddpg.h, minimarl_rmaddpg_collect.h: the recurrent trainer of rmaddpg / rmatd3 and its episode collector)
  *   mm_mlpbuf_*          PrioritizedMlpReplayBuffer / MlpReplayBuffer offpolicy/utils/mlp_buffer.py:10-340
  *   mm_eval_accum        greedy test loops                           vdn/_test.py:22-50; magym_runner.py:198-241
  */
@@ -1111,4 +1112,6 @@ int mm_debug_trace(uint64_t* host_out, int32_t n);
 #include "minimarl_maddpg_collect.h"
 /* the recurrent trainer rmaddpg / rmatd3 (mm_rmaddpg_*) likewise */
 #include "minimarl_rmaddpg.h"
+/* and its episode collector */
+#include "minimarl_rmaddpg_collect.h"
 #endif

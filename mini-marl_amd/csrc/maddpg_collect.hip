@@ -2,7 +2,8 @@
 // (collecter, offpolicy/runner/shared/magym_runner.py) with MADDPGPolicy.get_actions' discrete exploration
 // (algorithm/MADDPGPolicy.py:95-104) for E lockstep Checkers or Switch envs, a window of T steps from reset in ONE
 // launch, written as T E single transitions with reset-on-done inside the window. Window, fields, ring stores and env
-// tiles are those of moffq_collect.hip (collect_window.h); what differs is the action rule and where its noise is made.
+// tiles are those of moffq_collect.hip (collect_window.h); what differs is the action rule (collect_gumbel.h, shared with
+// the episode collector of rmaddpg / rmatd3) and where its noise is made.
 //
 //   net     the actor of maddpg.hip, LN(D) -> [Linear, ReLU, LN] x 2 -> Linear(A), in the MGeo<D, 64, 5> trunk layout:
 //           staged and evaluated by the exact-f32 v_mfma_f32_32x32x2_f32 fragment scheme of collect_tile.h (oc_stage_trunk,
@@ -25,6 +26,7 @@
 //           observe again (record 1 = next_obs) | barrier | stores; env lanes of done envs reset them | barrier.
 //           Every row observes twice a step; reusing record 1 as the next step's record 0 for envs that did not reset
 //           is left undone.
+#include "collect_gumbel.h"
 #include "collect_window.h"
 
 namespace mm {
@@ -34,47 +36,6 @@ struct MdcIo : McIo {
   uint64_t gumbel_seed;
   int explore;
 };
-
-// sg[i] = the Gumbel draw of tile row i / A, action i % A at step counter ctr, for i = i0, i0 + stride, .. < NA ne
-// (NA = N A: row i / A is agent (i % NA) / A of env e0 + i / NA, so the draw's second index n A + k is i % NA)
-__device__ __forceinline__ void mdc_noise(float* sg, uint64_t gseed, uint64_t ctr, int e0, int NA, int n, int i0,
-                                          int stride) {
-  for (int i = i0; i < n; i += stride) {
-    const int le = i / NA;
-    sg[i] = rng_gumbel(rng_draw(gseed, ctr, (uint64_t)(e0 + le), (uint64_t)(i - le * NA)));
-  }
-}
-
-// The action of a row from the head's result (every lane calls it; the row's owner lane writes): the first maximum of
-// logits (+ sg[row][A] when noisy), or with explore the counter RNG's action where u < eps. sact[row] gets the action,
-// lg[row][A] (global, may be null) the logits
-__device__ __forceinline__ void mdc_act(const MdcIo& a, f32x16 qa, bool owner, int row, uint64_t ctr, uint64_t rinner,
-                                        float eps, bool noisy, const float* sg, int* sact, float* lg) {
-  const float q4 = __shfl_xor(qa[0], 32);
-  if (owner) {
-    const float qv[OC_A] = {qa[0], qa[1], qa[2], qa[3], q4};
-    int g = 0;
-    float best = noisy ? qv[0] + sg[row * OC_A] : qv[0];
-#pragma unroll
-    for (int k = 1; k < OC_A; ++k) {
-      const float z = noisy ? qv[k] + sg[row * OC_A + k] : qv[k];
-      if (z > best) {
-        best = z;
-        g = k;
-      }
-    }
-    if (a.explore) {
-      const float u = rng_uniform(rng_draw_inner(a.seed, ctr, rinner));
-      const int ra = (int)rng_mod_small(rng_draw_inner(a.seed ^ 0x5bd1e995ull, ctr, rinner), OC_A);
-      g = u < eps ? ra : g;
-    }
-    sact[row] = g;
-    if (lg) {
-#pragma unroll
-      for (int k = 0; k < OC_A; ++k) lg[row * OC_A + k] = qv[k];
-    }
-  }
-}
 
 // (launch bounds: 3 waves per SIMD = three resident blocks per CU, which caps the kernel at 168 registers)
 template <class Env>
@@ -148,36 +109,6 @@ __global__ __launch_bounds__(256, 3) void maddpg_collect_kernel(TileArgs<MdcIo, 
     if (a.ret_out) a.ret_out[e0 + tid] = ret;
     if (a.ndone_out) a.ndone_out[e0 + tid] = nd;
   }
-}
-
-// the collectors' checks on the actor's dims, then the trainer's critic-width limit
-mm_offq_dims actor_dims(const mm_maddpg_dims* d) {
-  mm_offq_dims o = {};
-  if (d) {
-    o.n_agents = d->n_agents;
-    o.obs_dim = d->obs_dim;
-    o.hidden = d->hidden;
-    o.n_actions = d->n_actions;
-  }
-  return o;
-}
-
-int width_check(const char* who, const mm_offq_dims& o, int64_t E, int32_t T, bool rep) {
-  const bool wide = (int64_t)o.n_agents * (o.obs_dim + o.n_actions) > MM_MADDPG_MAX_CRITIC_WIDTH;
-  return report(who, wide ? "the critic input width N (D + A) is above MM_MADDPG_MAX_CRITIC_WIDTH" : nullptr, &o, E, T,
-                rep);
-}
-
-int check_checkers(const char* who, const mm_env* env, const mm_maddpg_dims* d, int64_t E, int32_t T, bool rep) {
-  const mm_offq_dims o = actor_dims(d);
-  const int rc = collect_check(who, env, d ? &o : nullptr, E, T, rep);
-  return rc ? rc : width_check(who, o, E, T, rep);
-}
-
-int check_switch(const char* who, const mm_switch* env, const mm_maddpg_dims* d, int64_t E, int32_t T, bool rep) {
-  const mm_offq_dims o = actor_dims(d);
-  const int rc = collect_switch_check(who, env, d ? &o : nullptr, E, T, rep);
-  return rc ? rc : width_check(who, o, E, T, rep);
 }
 
 int fill_mdc(MdcIo& a, const char* who, const float* PA, const mm_maddpg_collect_io* io, int64_t n_envs, int32_t T, int N,

@@ -24,111 +24,21 @@
 // action draw, the barriers and the stores. An env tile gives its argument struct and LDS layout, the staging of the
 // reset state, a row's current observation (the record the stores read and LayerNorm 0's output for the net), the env
 // lane's step with its private episode state, and where dones[t, e, n] comes from. The tiles, the trunk of the net
-// and the stores live in collect_tile.h, shared with the feed-forward transition collector (moffq_collect.hip):
+// and the stores live in collect_tile.h, shared with the feed-forward transition collectors; the staged GRU net, the
+// launch arguments and the launch in collect_gru.h, shared with the episode collector of rmaddpg / rmatd3
+// (rmaddpg_collect.hip):
 //   CheckersTile  dones[t, e, n] is the env's flag.
 //   SwitchTile  dones[t, e, n] is agent n's own done flag, dones_env[t, e] their conjunction.
 //
 // The env handle's live state is neither read nor written: every env starts from reset (Checkers: the handle's
 // init_grid / init_pos tables; Switch: the fixed start cells) and the episode's state lives in LDS only.
-#include "collect_tile.h"
+#include "collect_gru.h"
 
 namespace mm {
 namespace {
 
-// LDS layout of the staged net, float offsets (every weight image and vector starts on 16 bytes). KS1 = k-steps of
-// layer 1 (a multiple of 4, 2 KS1 >= D)
-template <int KS1>
-struct OcNetLds {
-  static constexpr int W1 = 0;                      // [2 rb][KS1 / 4][64][4]   col(s, h) = 2 s + h
-  static constexpr int W2 = W1 + 2 * KS1 * 64;      // [2 rb][8][64][4]   col(s, h) = 32 (s >> 4) + kperm(s & 15, h)
-  static constexpr int Wih = W2 + 2 * 32 * 64;      // [6 rb][8][64][4]
-  static constexpr int Whh = Wih + 6 * 32 * 64;     // [6 rb][8][64][4]
-  static constexpr int Wo = Whh + 6 * 32 * 64;      // [1 rb][8][64][4]   rows >= A zero
-  static constexpr int ln0w = Wo + 32 * 64;         // [2 h][KS1]: feature 2 s + h (D.. -> 0)
-  static constexpr int ln0b = ln0w + 2 * KS1;
-  static constexpr int b1 = ln0b + 2 * KS1, ln1w = b1 + 64, ln1b = ln1w + 64;
-  static constexpr int b2 = ln1b + 64, ln2w = b2 + 64, ln2b = ln2w + 64;
-  static constexpr int brz = ln2b + 64;             // [128] b_ih + b_hh of the r and z gates
-  static constexpr int bin = brz + 128, bhn = bin + 64;
-  static constexpr int lnrw = bhn + 64, lnrb = lnrw + 64;
-  static constexpr int bo = lnrb + 64;              // [32] (A.. zero)
-  static constexpr int net_end = bo + 32;
-  static_assert((KS1 & 3) == 0 && (ln0w & 3) == 0, "alignment");
-};
-
-using OcLds = CheckersLds<OcNetLds<24>, 1>;
-using OsLds = SwitchLds<OcNetLds<4>, 1>;
-static_assert(OcLds::total * 4 <= 160 * 1024, "LDS budget");
-static_assert(OsLds::total * 4 <= 160 * 1024, "LDS budget");
-using CheckersTile = CheckersTileT<OcLds>;
-using SwitchTile = SwitchTileT<OsLds>;
-
-// what both kernels take: the net, the exploration stream, the episode fields
-struct OcIo {
-  const float* P;
-  const float* eps;
-  const unsigned long long* counter;
-  uint64_t counter0, seed;
-  float *obs, *acts, *rew, *dones, *dones_env, *q_out, *ret_out;
-  int E, T, N, EB, max_steps, common;
-  float step_cost;
-};
 using OcArgs = TileArgs<OcIo, CheckersEnvArgs>;
 using OsArgs = TileArgs<OcIo, SwitchEnvArgs>;
-
-// stage the net (MGeo<D, 64, 5> flat layout at P) into the images and vectors of L; the caller's barrier follows
-template <typename L, int D, int KS1>
-__device__ __forceinline__ void oc_stage_net(float* sm, const float* __restrict__ P) {
-  using G = MGeo<D, OC_H, OC_A>;
-  const int tid = threadIdx.x;
-  oc_stage_trunk<L, D, KS1>(sm, P);
-  oc_pack<true>(sm + L::Wih, P + G::Wih, OC_H, 3 * OC_H, OC_H, 6, 32);
-  oc_pack<true>(sm + L::Whh, P + G::Whh, OC_H, 3 * OC_H, OC_H, 6, 32);
-  if (tid < OC_H) {
-    sm[L::brz + tid] = P[G::bih + tid] + P[G::bhh + tid];
-    sm[L::brz + OC_H + tid] = P[G::bih + OC_H + tid] + P[G::bhh + OC_H + tid];
-    sm[L::bin + tid] = P[G::bih + 2 * OC_H + tid];
-    sm[L::bhn + tid] = P[G::bhh + 2 * OC_H + tid];
-    sm[L::lnrw + tid] = P[G::lnr_w + tid];
-    sm[L::lnrb + tid] = P[G::lnr_b + tid];
-  }
-}
-
-// The net of one step from LayerNorm 0's output: x0[s] = this lane's normalised feature 2 s + h. Updates the hidden
-// state in place; Q 0..3 land in registers 0..3 of lane half 0 of the result, Q 4 in register 0 of half 1
-template <typename L, int KS1>
-__device__ __forceinline__ f32x16 oc_net(const float* sm, const float (&x0)[KS1], f32x16 (&hid)[2], int lane, int h) {
-  // ---- layer 1, layer 2
-  f32x16 f2[2];
-  oc_trunk<L, KS1>(sm, x0, f2, lane, h);
-  // ---- GRU: g[0..3] r | z pre-activations (input + hidden side), g[4..5] W_in x + b_in, g[6..7] W_hn h + b_hn
-  {
-    f32x16 g[8];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) g[kb] = oc_vec16(sm + L::brz + 32 * kb, h);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      g[4 + kb] = oc_vec16(sm + L::bin + 32 * kb, h);
-      g[6 + kb] = oc_vec16(sm + L::bhn + 32 * kb, h);
-    }
-    oc_mma<6, 32>(g, sm + L::Wih, lane, [&](int s) { return f2[s >> 4][s & 15]; });
-    oc_mma<4, 32>(g, sm + L::Whh, lane, [&](int s) { return hid[s >> 4][s & 15]; });
-    oc_mma<2, 32>(g + 6, sm + L::Whh + 4 * 8 * 256, lane, [&](int s) { return hid[s >> 4][s & 15]; });
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float rr = sigmoidf_(g[kb][r]), zz = sigmoidf_(g[2 + kb][r]);
-        const float nn = tanhf_(g[4 + kb][r] + rr * g[6 + kb][r]);
-        hid[kb][r] = nn + zz * (hid[kb][r] - nn);
-      }
-  }
-  // ---- head: LN, Linear(A)
-  f32x16 y[2] = {hid[0], hid[1]};
-  oc_ln(y, sm + L::lnrw, sm + L::lnrb, h);
-  return oc_head<L>(sm, y, lane, h);
-}
-
 
 // The episode loop, for either tile. Per step: observe, [t = T: store the final observation and stop,] net, action
 // draw | barrier | env step by the env lanes | barrier | the step's stores | barrier.
@@ -209,48 +119,6 @@ __global__ __launch_bounds__(256) void offq_collect_kernel(TileArgs<OcIo, typena
   if (a.ret_out && tid < ne) a.ret_out[e0 + tid] = ret;
 }
 
-// the launch arguments both kernels share; EB = envs of a block's tile
-int fill_io(OcIo& a, const char* who, const float* P, const mm_offq_collect_io* io, int64_t n_envs, int32_t T, int N,
-            int max_steps, float step_cost) {
-  MM_REQUIRE(P && io && io->eps && io->obs && io->acts && io->rewards && io->dones && io->dones_env,
-             "%s: null argument (P, io, eps and the five written fields are required)", who);
-  const void* al[] = {P, io->obs, io->acts, io->rewards, io->dones, io->dones_env, io->q_out};
-  for (const void* p : al) MM_REQUIRE(((uintptr_t)p & 15) == 0, "%s: P and the output fields must be 16-byte aligned", who);
-  a.P = P;
-  a.eps = io->eps;
-  a.counter = reinterpret_cast<const unsigned long long*>(io->counter);
-  a.counter0 = io->counter0;
-  a.seed = io->seed;
-  a.obs = io->obs;
-  a.acts = io->acts;
-  a.rew = io->rewards;
-  a.dones = io->dones;
-  a.dones_env = io->dones_env;
-  a.q_out = io->q_out;
-  a.ret_out = io->ret_out;
-  a.E = (int)n_envs;
-  a.T = T;
-  a.N = N;
-  a.EB = std::min(OC_ROWS / N, OC_MAXE);
-  a.max_steps = max_steps;
-  a.common = io->common_reward ? 1 : 0;
-  a.step_cost = step_cost;
-  return MM_OK;
-}
-
-// the launch of a tile's kernel: its dynamic-LDS attribute (set once per process), one block per EB envs
-template <class Env>
-int launch_collect(const TileArgs<OcIo, typename Env::EnvArgs>& a, int64_t n_envs, hipStream_t s) {
-  constexpr int lds = Env::L::total * 4;
-  static const hipError_t set_lds_attribute =
-      hipFuncSetAttribute((const void*)offq_collect_kernel<Env>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  MM_HIP_CHECK(set_lds_attribute);
-  const unsigned nb = (unsigned)((n_envs + a.EB - 1) / a.EB);
-  hipLaunchKernelGGL(offq_collect_kernel<Env>, dim3(nb), dim3(256), lds, s, a);
-  MM_HIP_CHECK(hipGetLastError());
-  return MM_OK;
-}
-
 }  // namespace
 }  // namespace mm
 
@@ -270,7 +138,7 @@ int mm_offq_collect(mm_env* env, const mm_offq_dims* d, const float* P, const mm
   rc = fill_io(a, "offq_collect", P, io, n_envs, T, ev.N, ev.max_steps, ev.step_cost);
   if (rc) return rc;
   static_cast<CheckersEnvArgs&>(a) = checkers_env_args(ev);
-  return launch_collect<CheckersTile>(a, n_envs, (hipStream_t)s);
+  return launch_episode<CheckersTile, offq_collect_kernel<CheckersTile>>(a, n_envs, (hipStream_t)s);
 }
 
 int mm_offq_collect_switch_supported(const mm_switch* env, const mm_offq_dims* d, int64_t n_envs, int32_t T) {
@@ -287,7 +155,7 @@ int mm_offq_collect_switch(mm_switch* env, const mm_offq_dims* d, const float* P
   rc = fill_io(a, "offq_collect_switch", P, io, n_envs, T, c.n_agents, c.max_steps, c.step_cost);
   if (rc) return rc;
   a.tab = env->tab;
-  return launch_collect<SwitchTile>(a, n_envs, (hipStream_t)s);
+  return launch_episode<SwitchTile, offq_collect_kernel<SwitchTile>>(a, n_envs, (hipStream_t)s);
 }
 
 }  // extern "C"

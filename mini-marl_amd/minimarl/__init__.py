@@ -9,7 +9,8 @@ from ._lib import lib, symbols  # noqa: F401
 _LAZY = {"OffQCollector": "offq_runner", "OffQRunner": "offq_runner",
          "MOffQCollector": "moffq_runner", "MOffQRunner": "moffq_runner",
          "MlpReplayBuffer": "mlpbuf", "PrioritizedMlpReplayBuffer": "mlpbuf", "MADDPG": "maddpg",
-         "MADDPGCollector": "maddpg_runner", "MADDPGRunner": "maddpg_runner", "RMADDPG": "rmaddpg"}
+         "MADDPGCollector": "maddpg_runner", "MADDPGRunner": "maddpg_runner", "RMADDPG": "rmaddpg",
+         "RMADDPGCollector": "rmaddpg_runner", "RMADDPGRunner": "rmaddpg_runner"}
 __all__ = ["lib", "symbols"] + list(_LAZY)
 
 

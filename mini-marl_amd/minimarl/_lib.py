@@ -560,3 +560,16 @@ _SIGS += [
     ("mm_rmaddpg_actor_grad", c_i32, [_MD, ctypes.POINTER(RmaddpgBatch), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     ("mm_rmaddpg_step", c_i32, [_MD, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 ]
+
+
+class RmaddpgCollectIO(OffqCollectIO):
+    """mm_rmaddpg_collect_io (include/minimarl_rmaddpg_collect.h): the members of mm_offq_collect_io (``w``), then these"""
+    _fields_ = [("gumbel_seed", c_u64), ("explore", c_i32)]
+
+
+_SIGS += [
+    ("mm_rmaddpg_collect_supported", c_i32, [c_vp, _MD, c_i64, c_i32]),
+    ("mm_rmaddpg_collect", c_i32, [c_vp, _MD, c_vp, ctypes.POINTER(RmaddpgCollectIO), c_i64, c_i32, c_vp]),
+    ("mm_rmaddpg_collect_switch_supported", c_i32, [c_vp, _MD, c_i64, c_i32]),
+    ("mm_rmaddpg_collect_switch", c_i32, [c_vp, _MD, c_vp, ctypes.POINTER(RmaddpgCollectIO), c_i64, c_i32, c_vp]),
+]

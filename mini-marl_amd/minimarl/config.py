@@ -142,7 +142,8 @@ class OffQTrainConfig:
     """offpolicy/config.py defaults of the episode-level QMix / VDN runner (minimarl.offq_runner.OffQRunner).
     ``n_envs`` is lockstep-specific: the episodes collected per iteration (the reference's ``num_envs``, fixed at 1
     there, base_runner.py:51)."""
-    # "qmix" | "vdn" (OffQRunner), "mqmix" | "mvdn" (MOffQRunner), "maddpg" | "matd3" (MADDPGRunner)
+    # "qmix" | "vdn" (OffQRunner), "mqmix" | "mvdn" (MOffQRunner), "maddpg" | "matd3" (MADDPGRunner),
+    # "rmaddpg" | "rmatd3" (RMADDPGRunner)
     algorithm_name: str = "qmix"
     n_envs: int = 32
     n_agents: int = 2

@@ -50,6 +50,10 @@ class OffQCollector:
     and the RNG step counter from device memory, so a captured ``launch()`` replays with whatever ``set_epsilon``
     / ``counter`` hold at replay time."""
 
+    # what a collector of another algorithm family replaces: the entry points (Checkers, Switch), their io struct and
+    # the policy's parameter vector the launch reads
+    _names, _io_type, _params = ("offq_collect", "offq_collect_switch"), OffqCollectIO, "P"
+
     def __init__(self, env, policy, T, seed, common_reward=True, with_q=False):
         self.env, self.policy = env, policy
         self.E, self.N, self.T = int(env.E), int(env.N), int(T)
@@ -57,11 +61,8 @@ class OffQCollector:
         self.device = policy.device
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.common_reward = bool(common_reward)
-        if isinstance(env, SwitchVecEnv):
-            self._name, supported = "offq_collect_switch", lib().mm_offq_collect_switch_supported
-        else:
-            self._name, supported = "offq_collect", lib().mm_offq_collect_supported
-        self._collect = getattr(lib(), "mm_" + self._name)
+        self._name = self._names[isinstance(env, SwitchVecEnv)]
+        self._collect, supported = getattr(lib(), "mm_" + self._name), getattr(lib(), "mm_" + self._name + "_supported")
         if not supported(env.handle(), ctypes.byref(policy.dims), self.E, self.T):
             # the launch reports why
             check(self._collect(env.handle(), ctypes.byref(policy.dims), None, None, self.E, self.T, None), self._name)
@@ -75,13 +76,16 @@ class OffQCollector:
         self.q = torch.zeros(T_, E, N, self.A, device=dev) if with_q else None
         self.eps = torch.zeros(1, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)   # counter0 of the next collect
-        io = OffqCollectIO()
+        self._io = self._make_io()
+
+    def _make_io(self):
+        io = self._io_type()
         io.eps, io.counter, io.counter0, io.seed = ptr(self.eps), ptr(self.counter), 0, self.seed
         io.common_reward = int(self.common_reward)
         for k in ("obs", "acts", "rewards", "dones", "dones_env"):
             setattr(io, k, ptr(self.fields[k]))
         io.q_out, io.ret_out = ptr(self.q), ptr(self.returns)
-        self._io = io
+        return io
 
     @property
     def share_obs(self):
@@ -94,7 +98,7 @@ class OffQCollector:
 
     def launch(self):
         """The collect launch and the counter advance (+T), nothing else: capturable in a HIP graph."""
-        check(self._collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(self.policy.P),
+        check(self._collect(self.env.handle(), ctypes.byref(self.policy.dims), ptr(getattr(self.policy, self._params)),
                             ctypes.byref(self._io), self.E, self.T, stream_handle(self.device)), self._name)
         self.counter.add_(self.T)
 
