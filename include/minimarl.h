@@ -780,6 +780,7 @@ typedef struct mm_offq_dims {
   int32_t n_agents, obs_dim, hidden, n_actions;
   int32_t mixer;                                   /* MM_OFFQ_VDN / MM_OFFQ_QMIX */
   int32_t state_dim, mixer_hidden, hyper_hidden;   /* QMIX: S, K (mixer_hidden_dim), hypernet_hidden_dim */
+  int32_t prev_act_inp;                            /* 1: the agent net's input row is [obs (D) | previous one-hot action (A)] */
 } mm_offq_dims;
 typedef struct mm_offq_batch {
   const float* obs; const float* share_obs; const float* acts; const float* rewards; const float* dones_env;
@@ -803,6 +804,18 @@ int mm_offq_loss_grad(const mm_offq_dims* d, const mm_offq_batch* b, const float
 int64_t mm_offq_qvals_workspace_bytes(const mm_offq_dims* d, int32_t L, int64_t R);
 int mm_offq_q_values(const mm_offq_dims* d, const float* P, const float* obs, const float* h0, float* q, float* h_out,
                      int32_t L, int64_t R, void* ws, int64_t ws_bytes, mm_stream_t s);
+/* prev_act_inp (QMixPolicy.py:38-45,68-74; qmix.py:127-153): with dims.prev_act_inp = 1 the agent net reads the
+ * row [obs (D) | previous one-hot action (A)], so its layout is the trunk layout at width D + A (ln0_w / ln0_b of
+ * D + A floats, W1 rows padded to ceil4(D + A)); obs_dim stays D and state_dim stays the mixer's S. The concatenated
+ * row is never stored: mm_offq_loss_grad gathers the action part from b->acts at step t - 1 of the same (agent,
+ * episode), exactly 0 at t = 0, for the behavior and the target net alike. mm_offq_param_counts,
+ * mm_offq_workspace_bytes and mm_offq_loss_grad follow the flag; mm_offq_q_values refuses it (MM_EINVAL) in favour
+ * of mm_offq_q_values_prev, which takes the previous actions of every stacked row as the caller has them:
+ * prev_acts [L, R, A], no time shift. Every other entry point that takes mm_offq_dims (mm_moffq_*, mm_offq_collect*,
+ * mm_moffq_collect*) refuses a non-zero flag with MM_EINVAL before any launch; their *_supported queries return 0. */
+int mm_offq_q_values_prev(const mm_offq_dims* d, const float* P, const float* obs, const float* prev_acts,
+                          const float* h0, float* q, float* h_out, int32_t L, int64_t R, void* ws, int64_t ws_bytes,
+                          mm_stream_t s);
 /* soft_update: target <- target * (1 - tau) + source * tau over n floats (tau = 1: hard update). */
 int mm_offq_soft_update(float* target, const float* source, int64_t n, double tau, mm_stream_t s);
 /* ------------------------------------------------------------------ offpolicy feed-forward QMix / VDN ("mqmix" / "mvdn")

@@ -514,9 +514,16 @@ inline int report(const char* who, const char* why, const mm_offq_dims* d, int64
   return why ? MM_EINVAL : MM_OK;
 }
 
+// the collectors feed the agent net the observation alone
+inline const char* no_prev_act() {
+  return "prev_act_inp is not built for the collectors (the trainer mm_offq_loss_grad has it)";
+}
+
 inline int collect_check(const char* who, const mm_env* env, const mm_offq_dims* d, int64_t E, int32_t T, bool rep) {
   const char* why = nullptr;
-  if (!env || !d) {
+  if (d && d->prev_act_inp) {
+    why = no_prev_act();
+  } else if (!env || !d) {
     why = "null env or dims";
   } else {
     const EnvDev& ev = env->d;
@@ -537,7 +544,9 @@ inline int collect_check(const char* who, const mm_env* env, const mm_offq_dims*
 inline int collect_switch_check(const char* who, const mm_switch* env, const mm_offq_dims* d, int64_t E, int32_t T,
                                 bool rep) {
   const char* why = nullptr;
-  if (!env || !d) {
+  if (d && d->prev_act_inp) {
+    why = no_prev_act();
+  } else if (!env || !d) {
     why = "null env or dims";
   } else {
     const mm_switch_cfg& c = env->cfg;

@@ -383,6 +383,7 @@ __global__ __launch_bounds__(256) void moffq_q_kernel(MqQArgs a) {
 int mq_check(const mm_offq_dims* d) {
   MM_REQUIRE(d && d->n_agents >= 1, "moffq: bad dims");
   MM_REQUIRE(d->mixer == MM_OFFQ_VDN || d->mixer == MM_OFFQ_QMIX, "moffq: mixer must be MM_OFFQ_VDN or MM_OFFQ_QMIX");
+  MM_REQUIRE(!d->prev_act_inp, "moffq: prev_act_inp is not built for the feed-forward trainer (mm_offq_loss_grad has it)");
   MM_REQUIRE(d->hidden == 64 && d->n_actions == 5 && (d->obs_dim == 3 || d->obs_dim == 47 || d->obs_dim == 94),
              "moffq: unsupported dims D=%d H=%d A=%d (supported: D 3|47|94, H 64, A 5)", d->obs_dim, d->hidden,
              d->n_actions);

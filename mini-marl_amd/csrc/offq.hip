@@ -48,6 +48,7 @@ enum { ST_MU0 = 0, ST_RS0, ST_MU1, ST_RS1, ST_MU2, ST_RS2, ST_MUR, ST_RSR, ST_N 
 struct OqPreArgs {
   const float* P[2];
   const float* obs;
+  const float* acts;                 // prev_act_inp: one-hot [N][T][B][A], or stacked [L][R][A]; else unused
   float* gi[2];
   float* a1; float* a2; float* st;   // behavior saves or NULL
   int64_t R1, NB;
@@ -82,13 +83,42 @@ __device__ __forceinline__ float4 bcast_get4(const float* slot, int i4) {
   return reinterpret_cast<const float4*>(slot)[i4];
 }
 
-__device__ __forceinline__ const float* obs_row(const float* obs, int stacked, int64_t r, int64_t NB, int B, int T1,
-                                                int D) {
-  if (stacked) return obs + r * D;
-  const int64_t t = r / NB, q = r - t * NB;
-  const int64_t i = q / B, b = q - i * B;
-  return obs + ((i * T1 + t) * B + b) * D;
-}
+// Source of one input row of the agent net, width D = DO + PA: the observation (DO floats) and, with prev_act_inp
+// (PA = A), the one-hot action of the previous step. The concatenated row [obs | prev act] exists nowhere in
+// memory: feature f is ONE load, from the observation row if f < DO, else from the batch's acts [N][T][B][A] at
+// step t - 1 of the same (agent, episode); at t = 0 (xa NULL) it is the constant 0 and nothing is loaded. The
+// address select is lane arithmetic ahead of the load, so a lane's gather stays a single independent load that the
+// one-row-ahead prefetch of offq_pre_kernel carries like a plain observation. Stacked rows (get_q_values) take row r
+// of obs [L][R][DO] and of the caller's prev_acts [L][R][A], with no time shift.
+template <int D, int PA>
+struct RowSrc {
+  static constexpr int DO = D - PA;
+  const float* xo;
+  const float* xa;
+  __device__ __forceinline__ RowSrc(const float* obs, const float* acts, int stacked, int64_t r, int64_t NB, int B,
+                                    int T1) {
+    if (stacked) {
+      xo = obs + r * DO;
+      xa = PA > 0 ? acts + r * PA : nullptr;
+      return;
+    }
+    const int64_t t = r / NB, q = r - t * NB;
+    const int64_t i = q / B, b = q - i * B;
+    xo = obs + ((i * T1 + t) * B + b) * DO;
+    xa = (PA > 0 && t > 0) ? acts + ((i * (T1 - 1) + (t - 1)) * B + b) * PA : nullptr;
+  }
+  // feature f < D of the row
+  __device__ __forceinline__ float feat(int f) const {
+    if constexpr (PA == 0) {
+      return xo[f];
+    } else {
+      const bool act = f >= DO;
+      if (act && !xa) return 0.f;
+      const float* p = act ? xa + (f - DO) : xo + f;
+      return *p;
+    }
+  }
+};
 
 // One wave per row at a time, lane j = feature j (H == 64; D <= 128 as two lane halves). The net's
 // W1 / W2 / W_ih rows are staged once per 1024-thread block into LDS with row strides of 4 x odd
@@ -101,7 +131,7 @@ template <int D> struct PreLds {
   static constexpr int oW2 = 64 * S1, oWih = oW2 + 64 * S2, oSlot = oWih + 192 * S2, total = oSlot + 16 * 128;
 };
 
-template <int D, int H, int A>
+template <int D, int H, int A, int PA>
 __global__ __launch_bounds__(1024) void offq_pre_kernel(OqPreArgs a) {
   static_assert(H == 64 && D <= 128, "lane-per-feature layout");
   using G = MGeo<D, H, A>;
@@ -138,19 +168,19 @@ __global__ __launch_bounds__(1024) void offq_pre_kernel(OqPreArgs a) {
   const float b2 = P[G::b2 + j], g2 = P[G::ln2_w + j], c2 = P[G::ln2_b + j];
   const float bir = P[G::bih + j], biz = P[G::bih + H + j], bin = P[G::bih + 2 * H + j];
   const bool save = y == 0 && a.a1;
-  // the next row's observation is loaded one row ahead
+  // the next row's input (observation and, with PA, previous action: RowSrc) is loaded one row ahead
   float xa_n = 0.f, xb_n = 0.f;
   if (wid < a.R1) {
-    const float* xp = obs_row(a.obs, a.stacked, wid, a.NB, a.B, a.T1, D);
-    xa_n = j < D0 ? xp[j] : 0.f;
-    xb_n = j < D1 ? xp[64 + j] : 0.f;
+    const RowSrc<D, PA> xp(a.obs, a.acts, a.stacked, wid, a.NB, a.B, a.T1);
+    xa_n = j < D0 ? xp.feat(j) : 0.f;
+    xb_n = j < D1 ? xp.feat(64 + j) : 0.f;
   }
   for (int64_t r = wid; r < a.R1; r += nw) {
     const float xa = xa_n, xb = xb_n;
     if (r + nw < a.R1) {
-      const float* xp = obs_row(a.obs, a.stacked, r + nw, a.NB, a.B, a.T1, D);
-      xa_n = j < D0 ? xp[j] : 0.f;
-      xb_n = j < D1 ? xp[64 + j] : 0.f;
+      const RowSrc<D, PA> xp(a.obs, a.acts, a.stacked, r + nw, a.NB, a.B, a.T1);
+      xa_n = j < D0 ? xp.feat(j) : 0.f;
+      xb_n = j < D1 ? xp.feat(64 + j) : 0.f;
     }
     // LN0
     const float mu0 = wave_sum(xa + xb) / (float)D;
@@ -874,14 +904,14 @@ __global__ __launch_bounds__(256) void offq_rec_bwd_kernel(OqRecBwdArgs a) {
 // so every transposed mat-vec is 64 readlane broadcasts + FMAs; the LayerNorm backward sums are
 // wave reductions. Writes the GF operands of the weight-gradient reduction (tiled SoA).
 struct OqPreBwdArgs {
-  const float* P; const float* obs; const float* a1; const float* a2; const float* st; const float* hs;
+  const float* P; const float* obs; const float* acts; const float* a1; const float* a2; const float* st; const float* hs;
   const float* dg;
   float* gsoa;
   int64_t Rb, NB;
   int T1, B;
 };
 
-template <int D, int H, int A>
+template <int D, int H, int A, int PA>
 __global__ __launch_bounds__(256) void offq_pre_bwd_kernel(OqPreBwdArgs a) {
   static_assert(H == 64 && D <= 128, "lane-per-feature layout");
   using G = MGeo<D, H, A>;
@@ -1003,16 +1033,17 @@ __global__ __launch_bounds__(256) void offq_pre_bwd_kernel(OqPreBwdArgs a) {
         if constexpr (D1 > 0) x1 = fmaf(c1bb[4 * c + u], tv[u], x1);
       }
     }
-    const float* xp = obs_row(a.obs, 0, r, a.NB, a.B, a.T1, D);
+    // x-hat of LN0 from the same gather as the forward (its statistics are those of the whole [obs | prev act] row)
+    const RowSrc<D, PA> xp(a.obs, a.acts, 0, r, a.NB, a.B, a.T1);
     const float mu0 = sp[ST_MU0], rs0 = sp[ST_RS0];
     if (k < D0) {
-      const float xh0 = (xp[k] - mu0) * rs0;
+      const float xh0 = (xp.feat(k) - mu0) * rs0;
       put(F::DF0 + k, x0);
       put(F::P0 + k, x0 * xh0);
       put(F::F0 + k, xh0 * g0a + b0a);
     }
     if (k < D1) {
-      const float xh0 = (xp[64 + k] - mu0) * rs0;
+      const float xh0 = (xp.feat(64 + k) - mu0) * rs0;
       put(F::DF0 + 64 + k, x1);
       put(F::P0 + 64 + k, x1 * xh0);
       put(F::F0 + 64 + k, xh0 * g0b + b0b);
@@ -1086,8 +1117,10 @@ static int64_t mixer_offsets(const mm_offq_dims* d, int64_t o[15]) {
   return c;
 }
 
-template <int D, int H, int A>
+// D: the agent net's input width; PA = A with prev_act_inp (the batch's observations are then D - PA wide), else 0
+template <int D, int H, int A, int PA = 0>
 struct OffqShape {
+  static_assert(PA == 0 || PA == A, "the previous action is one one-hot of A");
   using G = MGeo<D, H, A>;
   using TW = TrunkWgrad<D, H>;
 
@@ -1204,6 +1237,7 @@ struct OffqShape {
     pa.P[0] = P;
     pa.P[1] = PT;
     pa.obs = bt->obs;
+    pa.acts = bt->acts;
     pa.gi[0] = ws + w.gi;
     pa.gi[1] = ws + w.gi + w.R1 * 3 * H;
     pa.a1 = ws + w.a1;
@@ -1213,7 +1247,7 @@ struct OffqShape {
     pa.NB = w.NB;
     pa.T1 = T + 1;
     pa.B = B;
-    hipLaunchKernelGGL((offq_pre_kernel<D, H, A>), dim3(lds_blocks(w.R1, 2), 2), dim3(1024),
+    hipLaunchKernelGGL((offq_pre_kernel<D, H, A, PA>), dim3(lds_blocks(w.R1, 2), 2), dim3(1024),
                        (size_t)PreLds<D>::total * 4, s, pa);
     MM_HIP_CHECK(hipGetLastError());
     OqRecArgs ra = {};
@@ -1378,6 +1412,7 @@ struct OffqShape {
     OqPreBwdArgs pb = {};
     pb.P = P;
     pb.obs = bt->obs;
+    pb.acts = bt->acts;
     pb.a1 = ws + w.a1;
     pb.a2 = ws + w.a2;
     pb.st = ws + w.st;
@@ -1388,26 +1423,28 @@ struct OffqShape {
     pb.NB = w.NB;
     pb.T1 = T + 1;
     pb.B = B;
-    hipLaunchKernelGGL((offq_pre_bwd_kernel<D, H, A>), dim3(wave_blocks(w.Rb)), dim3(256), 0, s, pb);
+    hipLaunchKernelGGL((offq_pre_bwd_kernel<D, H, A, PA>), dim3(wave_blocks(w.Rb)), dim3(256), 0, s, pb);
     MM_HIP_CHECK(hipGetLastError());
     return TW::template wgrad<A>(ws + w.gsoa, w.rsb, grad, ws + w.wpart, s);
   }
 
   static int64_t qvals_ws(int L, int64_t R) { return al64((int64_t)L * R * 3 * H) + al64((int64_t)L * R * H); }
 
-  static int q_values(const float* P, const float* obs, const float* h0, float* q, float* hout, int L, int64_t R,
-                      float* ws, hipStream_t s) {
+  // prev: [L][R][A] previous one-hot actions of the stacked rows (PA > 0), else unused
+  static int q_values(const float* P, const float* obs, const float* prev, const float* h0, float* q, float* hout,
+                      int L, int64_t R, float* ws, hipStream_t s) {
     const int64_t R1 = (int64_t)L * R;
     OqPreArgs pa = {};
     pa.P[0] = P;
     pa.obs = obs;
+    pa.acts = prev;
     pa.gi[0] = ws;
     pa.R1 = R1;
     pa.NB = R;
     pa.T1 = L;
     pa.B = 1;
     pa.stacked = 1;
-    hipLaunchKernelGGL((offq_pre_kernel<D, H, A>), dim3(lds_blocks(R1, 1), 1), dim3(1024),
+    hipLaunchKernelGGL((offq_pre_kernel<D, H, A, PA>), dim3(lds_blocks(R1, 1), 1), dim3(1024),
                        (size_t)PreLds<D>::total * 4, s, pa);
     MM_HIP_CHECK(hipGetLastError());
     OqRecArgs ra = {};
@@ -1437,31 +1474,35 @@ struct OffqShape {
   static int set_lds() {
     static bool done = false;
     if (done) return MM_OK;
-    MM_HIP_CHECK(hipFuncSetAttribute((const void*)offq_pre_kernel<D, H, A>,
+    MM_HIP_CHECK(hipFuncSetAttribute((const void*)offq_pre_kernel<D, H, A, PA>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, PreLds<D>::total * 4));
     done = true;
     return MM_OK;
   }
 };
 
+// one shape per (obs_dim, prev_act_inp): the net's width is obs_dim, or obs_dim + 5 with the previous action
+#define MM_OFFQ_CASE(d, DOBS, PA, CALL)                                                            \
+  if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == DOBS && ((d)->prev_act_inp != 0) == (PA != 0)) { \
+    using SH = mm::OffqShape<DOBS + PA, 64, 5, PA>;                                                \
+    return CALL;                                                                                   \
+  }
 #define MM_OFFQ_DISPATCH(d, CALL)                                                                  \
   do {                                                                                             \
-    if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == 3) {                           \
-      using SH = mm::OffqShape<3, 64, 5>;                                                           \
-      return CALL;                                                                                 \
-    }                                                                                              \
-    if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == 47) {                          \
-      using SH = mm::OffqShape<47, 64, 5>;                                                          \
-      return CALL;                                                                                 \
-    }                                                                                              \
-    if ((d)->hidden == 64 && (d)->n_actions == 5 && (d)->obs_dim == 94) {                          \
-      using SH = mm::OffqShape<94, 64, 5>;                                                          \
-      return CALL;                                                                                 \
-    }                                                                                              \
-    mm::set_error("offq: unsupported dims D=%d H=%d A=%d (supported: D 3|47|94, H 64, A 5)", (d)->obs_dim, \
-                  (d)->hidden, (d)->n_actions);                                                    \
+    MM_OFFQ_CASE(d, 3, 0, CALL)                                                                    \
+    MM_OFFQ_CASE(d, 47, 0, CALL)                                                                   \
+    MM_OFFQ_CASE(d, 94, 0, CALL)                                                                   \
+    MM_OFFQ_CASE(d, 3, 5, CALL)                                                                    \
+    MM_OFFQ_CASE(d, 47, 5, CALL)                                                                   \
+    MM_OFFQ_CASE(d, 94, 5, CALL)                                                                   \
+    mm::set_error("offq: unsupported dims D=%d H=%d A=%d (supported: D 3|47|94, H 64, A 5; prev_act_inp 0|1)",     \
+                  (d)->obs_dim, (d)->hidden, (d)->n_actions);                                      \
     return MM_EINVAL;                                                                              \
   } while (0)
+
+static int ws_bytes_of(const mm_offq_dims* d, int T, int B, int64_t* n) {
+  MM_OFFQ_DISPATCH(d, (*n = SH::layout(d, T, B).total * 4, MM_OK));
+}
 
 static int check_dims(const mm_offq_dims* d) {
   MM_REQUIRE(d && d->n_agents >= 1, "offq: bad dims");
@@ -1501,10 +1542,8 @@ int mm_offq_mixer_offsets(const mm_offq_dims* d, int64_t offs[15]) {
 
 int64_t mm_offq_workspace_bytes(const mm_offq_dims* d, int32_t T, int32_t B) {
   if (mm::check_dims(d) || T < 1 || B < 1) return -1;
-  if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 3) return mm::OffqShape<3, 64, 5>::layout(d, T, B).total * 4;
-  if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 47) return mm::OffqShape<47, 64, 5>::layout(d, T, B).total * 4;
-  if (d->hidden == 64 && d->n_actions == 5 && d->obs_dim == 94) return mm::OffqShape<94, 64, 5>::layout(d, T, B).total * 4;
-  return -1;
+  int64_t n = -1;
+  return mm::ws_bytes_of(d, T, B, &n) ? -1 : n;
 }
 
 int mm_offq_loss_grad(const mm_offq_dims* d, const mm_offq_batch* b, const float* P, const float* PT, float* grad,
@@ -1531,9 +1570,23 @@ int64_t mm_offq_qvals_workspace_bytes(const mm_offq_dims* d, int32_t L, int64_t 
 int mm_offq_q_values(const mm_offq_dims* d, const float* P, const float* obs, const float* h0, float* q, float* h_out,
                      int32_t L, int64_t R, void* ws, int64_t ws_bytes, mm_stream_t s) {
   MM_REQUIRE(d && P && obs && q && ws && L >= 1 && R >= 1, "offq_q_values: bad args");
+  MM_REQUIRE(!d->prev_act_inp, "offq_q_values: dims.prev_act_inp is set: call mm_offq_q_values_prev with the rows' "
+                               "previous actions");
   const int64_t need = mm_offq_qvals_workspace_bytes(d, L, R);
   MM_REQUIRE(need > 0 && ws_bytes >= need, "offq_q_values: workspace too small");
-  MM_OFFQ_DISPATCH(d, (SH::set_lds() ? MM_EHIP : SH::q_values(P, obs, h0, q, h_out, L, R, (float*)ws, (hipStream_t)s)));
+  MM_OFFQ_DISPATCH(d, (SH::set_lds() ? MM_EHIP
+                                     : SH::q_values(P, obs, nullptr, h0, q, h_out, L, R, (float*)ws, (hipStream_t)s)));
+}
+
+int mm_offq_q_values_prev(const mm_offq_dims* d, const float* P, const float* obs, const float* prev_acts,
+                          const float* h0, float* q, float* h_out, int32_t L, int64_t R, void* ws, int64_t ws_bytes,
+                          mm_stream_t s) {
+  MM_REQUIRE(d && P && obs && prev_acts && q && ws && L >= 1 && R >= 1, "offq_q_values_prev: bad args");
+  MM_REQUIRE(d->prev_act_inp, "offq_q_values_prev: dims.prev_act_inp is 0: call mm_offq_q_values");
+  const int64_t need = mm_offq_qvals_workspace_bytes(d, L, R);
+  MM_REQUIRE(need > 0 && ws_bytes >= need, "offq_q_values_prev: workspace too small");
+  MM_OFFQ_DISPATCH(d, (SH::set_lds() ? MM_EHIP
+                                     : SH::q_values(P, obs, prev_acts, h0, q, h_out, L, R, (float*)ws, (hipStream_t)s)));
 }
 
 int mm_offq_soft_update(float* target, const float* source, int64_t n, double tau, mm_stream_t s) {

@@ -213,8 +213,11 @@ struct WgJobDev {
   int M, K, ldw, blk0, nblk;
   int64_t part;  // offset of this job's partials: nblk x (M*K + M)
 };
+// job slots of one launch: a trunk net has 16 jobs up to D = 96 and 18 for 96 < D <= 128 (the D-row LN0 jobs split
+// at 96 rows); TrunkWgrad::wgrad static_asserts its count against this
+constexpr int kWgMaxJobs = 20;
 struct WgArgsDev {
-  WgJobDev job[MM_MAPPO_MAX_JOBS];
+  WgJobDev job[kWgMaxJobs];
   int njobs;
   int nf;  // fields of the tiled SoA operand array (tile stride nf * 64)
   int64_t Rs, rows_per_block;
@@ -374,6 +377,12 @@ struct TrunkWgrad {
     add(F::P0, D, 0, 0, 0, 0, G::ln0_w);
     return nj;
   }
+  // the number of jobs that jobs<O>() writes: an M x K product splits into ceil(M / 96) x ceil(K / 64) jobs
+  static constexpr int split(int M, int K) { return ((M + 95) / 96) * (K > 0 ? (K + 63) / 64 : 1); }
+  template <int O>
+  static constexpr int n_jobs() {
+    return split(O, H) + 2 * split(3 * H, H) + split(H, H) + split(H, D) + 6 * split(H, 0) + 2 * split(D, 0);
+  }
   static int64_t rows_per_block(int64_t Rs) {
     int64_t rpb = (Rs + 399) / 400;
     rpb = (rpb + 127) / 128 * 128;
@@ -381,6 +390,7 @@ struct TrunkWgrad {
   }
   template <int O>
   static int wgrad(const float* gsoa, int64_t Rs, float* grad, float* partial, hipStream_t s) {
+    static_assert(n_jobs<O>() <= kWgMaxJobs, "more weight-gradient jobs than WgArgsDev holds");
     WgArgsDev w = {};
     w.Rs = Rs;
     w.rows_per_block = rows_per_block(Rs);

@@ -359,7 +359,7 @@ MM_OFFQ_VDN, MM_OFFQ_QMIX = 0, 1
 
 class OffqDims(ctypes.Structure):
     _fields_ = [("n_agents", c_i32), ("obs_dim", c_i32), ("hidden", c_i32), ("n_actions", c_i32), ("mixer", c_i32),
-                ("state_dim", c_i32), ("mixer_hidden", c_i32), ("hyper_hidden", c_i32)]
+                ("state_dim", c_i32), ("mixer_hidden", c_i32), ("hyper_hidden", c_i32), ("prev_act_inp", c_i32)]
 
 
 class OffqBatch(ctypes.Structure):
@@ -376,6 +376,7 @@ _SIGS += [
     ("mm_offq_loss_grad", c_i32, [_OD, ctypes.POINTER(OffqBatch), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     ("mm_offq_qvals_workspace_bytes", c_i64, [_OD, c_i32, c_i64]),
     ("mm_offq_q_values", c_i32, [_OD, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
+    ("mm_offq_q_values_prev", c_i32, [_OD, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     ("mm_offq_soft_update", c_i32, [c_vp, c_vp, c_i64, c_f64, c_vp]),
 ]
 

@@ -46,7 +46,7 @@ class OffQMix:
     def __init__(self, n_agents, obs_dim, n_actions, episode_length, batch_size, mixer="qmix", hidden=64,
                  mixer_hidden=32, hyper_hidden=64, gamma=0.99, lr=5e-4, opti_eps=1e-5, max_grad_norm=10.0,
                  use_double_q=True, use_per=True, use_huber_loss=False, huber_delta=10.0, per_nu=0.9,
-                 per_eps=1e-6, tau=0.005, device="cuda", seed=None, grad_allreduce=None):
+                 per_eps=1e-6, tau=0.005, device="cuda", seed=None, grad_allreduce=None, prev_act_inp=False):
         assert mixer in ("qmix", "vdn")
         if mixer == "qmix" and int(mixer_hidden) > MAX_MIXER_HIDDEN:
             raise ValueError(f"OffQMix: mixer_hidden {int(mixer_hidden)} is above the limit of {MAX_MIXER_HIDDEN} "
@@ -64,8 +64,11 @@ class OffQMix:
         # samples its own episode shard, so each rank's loss keeps its own mask-count denominator
         self.allreduce = grad_allreduce
         self.device = torch.device(device)
+        # prev_act_inp (QMixPolicy.py:38-45): the agent net reads [obs | previous one-hot action], width D + A; the
+        # kernels gather that row from the batch's obs and acts, so self.D stays the observation width
+        self.prev_act_inp = bool(prev_act_inp)
         self.dims = OffqDims(self.N, self.D, self.H, self.A, MM_OFFQ_QMIX if mixer == "qmix" else MM_OFFQ_VDN,
-                             self.S, self.K, self.Hh)
+                             self.S, self.K, self.Hh, int(self.prev_act_inp))
         L = lib()
         na, nm = c_i64(), c_i64()
         check(L.mm_offq_param_counts(ctypes.byref(self.dims), ctypes.byref(na), ctypes.byref(nm)), "offq_param_counts")
@@ -74,7 +77,7 @@ class OffQMix:
         mo = (c_i64 * 15)()
         check(L.mm_offq_mixer_offsets(ctypes.byref(self.dims), mo), "offq_mixer_offsets")
         self.moffs = list(mo)
-        self.Dp, self.Ap = (self.D + 3) // 4 * 4, (self.A + 3) // 4 * 4
+        self.Dp, self.Ap = (self.Din + 3) // 4 * 4, (self.A + 3) // 4 * 4
         H, Dp, Ap = self.H, self.Dp, self.Ap
         sz = [Dp, Dp, H * Dp, H, H, H, H * H, H, H, H, 3 * H * H, 3 * H * H, 3 * H, 3 * H, H, H, Ap * H, Ap]
         self.aoffs = list(np.concatenate([[0], np.cumsum(sz)]).astype(np.int64))
@@ -100,8 +103,15 @@ class OffQMix:
             self.hard_target_updates()
 
     # -- parameter views ---------------------------------------------------------------------
+    prev_act_inp = False        # default for subclasses with an __init__ of their own (MOffQMix)
+
+    @property
+    def Din(self):
+        """Input width of the agent net: D, or D + A with prev_act_inp."""
+        return self.D + (self.A if self.prev_act_inp else 0)
+
     def agent_shape(self, key):
-        D, H, A = self.D, self.H, self.A
+        D, H, A = self.Din, self.H, self.A
         return {"ln0_w": (D,), "ln0_b": (D,), "W1": (H, D), "b1": (H,), "ln1_w": (H,), "ln1_b": (H,),
                 "W2": (H, H), "b2": (H,), "ln2_w": (H,), "ln2_b": (H,), "Wih": (3 * H, H), "Whh": (3 * H, H),
                 "bih": (3 * H,), "bhh": (3 * H,), "lnr_w": (H,), "lnr_b": (H,), "Wo": (A, H), "bo": (A,)}[key]
@@ -110,7 +120,7 @@ class OffQMix:
         t = self.P if t is None else t
         o = self.aoffs[AGENT_KEYS.index(key)]
         if key == "W1":
-            return t[o:o + self.H * self.Dp].view(self.H, self.Dp)[:, :self.D]
+            return t[o:o + self.H * self.Dp].view(self.H, self.Dp)[:, :self.Din]
         if key == "Wo":
             return t[o:o + self.Ap * self.H].view(self.Ap, self.H)[:self.A]
         n = int(np.prod(self.agent_shape(key)))
@@ -218,11 +228,16 @@ class OffQMix:
 
     # -- checkpoint (minimarl.checkpoint) ------------------------------------------------------
     def checkpoint_tensors(self):
-        return ({"P": self.P, "PT": self.PT, "m": self.m, "v": self.v, "step": self.step},
-                {"mixer": self.mixer_kind})
+        scalars = {"mixer": self.mixer_kind}
+        if self.prev_act_inp:
+            scalars["prev_act_inp"] = True
+        return {"P": self.P, "PT": self.PT, "m": self.m, "v": self.v, "step": self.step}, scalars
 
     def restore_tensors(self, ts, scalars):
         from .checkpoint import copy_into
+        if bool(scalars.get("prev_act_inp", False)) != self.prev_act_inp:
+            raise ValueError(f"OffQMix: the checkpoint was written with prev_act_inp="
+                             f"{bool(scalars.get('prev_act_inp', False))}, this trainer has {self.prev_act_inp}")
         for k in ("P", "PT", "m", "v", "step"):
             copy_into(getattr(self, k), ts[k], k)
 
@@ -233,14 +248,26 @@ class OffQMix:
             return torch.zeros(batch_size, self.H, device=self.device)
         return torch.zeros(num_agents, batch_size, self.H, device=self.device)
 
-    def get_q_values(self, obs, rnn_states=None, target=False):
-        """QMixPolicy.get_q_values (prev_act_inp off): obs [R, D] or [L, R, D], hidden [R, H] ->
-        (q [R, A] or [L, R, A], new hidden [R, H])."""
+    def get_q_values(self, obs, rnn_states=None, target=False, prev_actions=None):
+        """QMixPolicy.get_q_values (QMixPolicy.py:51-83): obs [R, D] or [L, R, D], hidden [R, H] ->
+        (q [R, A] or [L, R, A], new hidden [R, H]). With prev_act_inp, ``prev_actions`` (one-hot floats shaped like
+        obs with A in place of D) is required and is what the reference's caller concatenates: no time shift is
+        applied here. Without it, a ``prev_actions`` is an error (the reference would ignore it)."""
+        if self.prev_act_inp and prev_actions is None:
+            raise ValueError("OffQMix.get_q_values: prev_act_inp is set, prev_actions is required")
+        if not self.prev_act_inp and prev_actions is not None:
+            raise ValueError("OffQMix.get_q_values: prev_actions given but prev_act_inp is off")
         x = self._dev(obs)
         seq = x.dim() == 3
         if not seq:
             x = x.unsqueeze(0)
         Ls, R = int(x.shape[0]), int(x.shape[1])
+        assert int(x.shape[2]) == self.D, x.shape
+        pa = None
+        if self.prev_act_inp:
+            pa = self._dev(prev_actions)
+            pa = pa if seq else pa.unsqueeze(0)
+            assert tuple(pa.shape) == (Ls, R, self.A), pa.shape
         key = (Ls, R)
         if key not in self._qws:
             nb = int(lib().mm_offq_qvals_workspace_bytes(ctypes.byref(self.dims), Ls, R))
@@ -250,14 +277,18 @@ class OffQMix:
         q = torch.empty(Ls, R, self.A, device=self.device)
         h2 = torch.empty(R, self.H, device=self.device)
         h0 = None if rnn_states is None else self._dev(rnn_states).reshape(R, self.H)
-        check(lib().mm_offq_q_values(ctypes.byref(self.dims), ptr(self.PT if target else self.P), ptr(x), ptr(h0),
-                                     ptr(q), ptr(h2), Ls, R, ptr(ws), nb, stream_handle(self.device)),
-              "offq_q_values")
+        P, st = ptr(self.PT if target else self.P), stream_handle(self.device)
+        if pa is None:
+            check(lib().mm_offq_q_values(ctypes.byref(self.dims), P, ptr(x), ptr(h0), ptr(q), ptr(h2), Ls, R, ptr(ws),
+                                         nb, st), "offq_q_values")
+        else:
+            check(lib().mm_offq_q_values_prev(ctypes.byref(self.dims), P, ptr(x), ptr(pa), ptr(h0), ptr(q), ptr(h2),
+                                              Ls, R, ptr(ws), nb, st), "offq_q_values_prev")
         return (q if seq else q[0]), h2
 
-    def get_actions(self, obs, rnn_states=None):
+    def get_actions(self, obs, rnn_states=None, prev_actions=None):
         """Greedy get_actions (explore=False, QMixPolicy.py:117-195): one-hot actions [R, A], new
         hidden, greedy Q [R, 1]."""
-        q, h2 = self.get_q_values(obs, rnn_states)
+        q, h2 = self.get_q_values(obs, rnn_states, prev_actions=prev_actions)
         gq, ga = q.max(-1)
         return torch.nn.functional.one_hot(ga, self.A).float(), h2, gq.unsqueeze(-1)

@@ -55,6 +55,9 @@ class OffQCollector:
     _names, _io_type, _params = ("offq_collect", "offq_collect_switch"), OffqCollectIO, "P"
 
     def __init__(self, env, policy, T, seed, common_reward=True, with_q=False):
+        if getattr(policy, "prev_act_inp", False):
+            raise NotImplementedError("OffQCollector: prev_act_inp is not built for the one-launch collector (the "
+                                      "trainer and get_q_values have it)")
         self.env, self.policy = env, policy
         self.E, self.N, self.T = int(env.E), int(env.N), int(T)
         self.D, self.A = int(policy.D), int(policy.A)
